@@ -14,13 +14,19 @@ A shard exceeds one MI355X's 288 GB of HBM, so its blocks stream through a
 resident 2M-block (64 GiB) arena; before each pass the on-device generator
 writes that pass's own logical blocks. The regeneration has its
 own HIP events and is taken out of the step time, so `value` covers the hash
-launches, the Merkle tree and the gather. Every block hashed is distinct, and the
-printed root is checked against the libxxhash fixture of the same workload
+launches, the Merkle tree and the gather. Every block hashed is distinct, and with
+--full the printed root is checked against the libxxhash fixture of the same workload
 (tests/golden/c3c4_roots.json): a mismatch exits non-zero.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL)
     python bench.py --gpus N ...   (no launcher: bench.py spawns the N ranks itself)
+
+A plain run does what the headline figure needs: set up, settle and warm up, time the K
+steps, print the line. --full adds what takes runs of its own or reads a reference: the
+CPU baselines, the measured read peak, the gather workload's uniform-kernel rerun and the
+comparison of the c3 / c4 roots with their libxxhash fixture (a mismatch exits non-zero).
+--dump-outputs DIR writes what the last timed step returned (checksums, root) as .npy.
 """
 from __future__ import annotations
 
@@ -62,8 +68,15 @@ def parse():
     p.add_argument("--alloc", default="plain", choices=sorted(ALLOC_MODES),
                    help="arena placement: plain = hipMalloc (stormck_device_alloc); with the probe build "
                         "(STORMCK_LIBRARY=tools/libstormck_probes.so) also contig = hipDeviceMallocContiguous")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (rank 0, N=1)")
-    p.add_argument("--no-cpu", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: CPU baselines, the measured read peak, "
+                        "the gather workload's uniform-kernel rerun, the c3 / c4 root against its fixture")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="c3 / c4: after the timed steps write what the last step computed to DIR/<name>.npy "
+                        "(float64): the leaf checksums (a fixed seeded sample of them above 1M blocks) and the root")
+    p.add_argument("--cpu-seconds", type=float, default=12.0,
+                   help="with --full: CPU baseline sample budget (rank 0, N=1)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baselines out")
     p.add_argument("--settle", type=float, default=1.0,
                    help="before the W warmup steps, run untimed steps for at least this many seconds so the "
                         "GPU clocks settle (short workloads otherwise time a ramping clock)")
@@ -123,6 +136,54 @@ def settle(step, seconds: float, group_dev=None):
 def va_alignment(ptr: int) -> int:
     """Largest power of two (up to 2^40) that divides a virtual address."""
     return min(ptr & -ptr, 1 << 40) if ptr else 0
+
+
+DUMP_SAMPLE = 1 << 20   # --dump-outputs: checksums written per array (16 MiB as float64 pairs)
+DUMP_LIMIT = 64 << 20   # --dump-outputs: bytes written in all, at most
+
+
+def dump_indices(n: int, most: int = DUMP_SAMPLE):
+    """The checksums --dump-outputs writes of an n-block output: all of them up to
+    `most`, above that the first, the last and a seeded sample, ascending (the same
+    indices in every run and every build)."""
+    import numpy as np
+    if n <= most:
+        return np.arange(n, dtype=np.int64)
+    pick = np.random.default_rng(SYNTH_SEED).choice(n, size=most - 2, replace=False)
+    return np.union1d(pick, [0, n - 1]).astype(np.int64)
+
+
+def u64_halves(values):
+    """64-bit words as float64 pairs (high 32 bits, low 32 bits): exact, so two builds'
+    dumps compare bit for bit."""
+    import numpy as np
+    u = np.ascontiguousarray(values).view(np.uint64)
+    return np.stack([(u >> np.uint64(32)).astype(np.float64), (u & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def root_words(root):
+    """A root Pointer (checksum, address, revision, type) as four uint64 words."""
+    import numpy as np
+    return np.array([int(v) & (2**64 - 1) for v in root], dtype=np.uint64)
+
+
+def dump_outputs(dirname: str, arrays: dict):
+    """Write each array as dirname/<name>.npy in float64."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(np.asarray(v).size * 8 for v in arrays.values())
+    if total > DUMP_LIMIT:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT}-byte limit")
+    for name, v in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
+
+
+def dump_checksums(cs, n: int, most: int = DUMP_SAMPLE):
+    """(checksums as float64 halves, their block indices) of a device int64 checksum tensor."""
+    import torch
+    idx = dump_indices(n, most)
+    picked = cs[torch.from_numpy(idx).to(cs.device)].cpu().numpy()
+    return u64_halves(picked), idx.astype("float64")
 
 
 def measured_read_peak(arena_ptr: int, arena_n: int, stream, achieved: float):
@@ -297,7 +358,7 @@ def commit_workload(a):
     fx = golden("c3c4_roots.json")
     want = fx["f1_commit_1m"]["root"][0] if fx and "f1_commit_1m" in fx and n == fx["f1_commit_1m"]["leaves"] else None
     res["root_check"], rc = check_against(int(cs[-1]), want, "f1_commit_1m, tests/golden/c3c4_roots.json")
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         res["cpu_baseline"] = cpu_commit_baseline(a.cpu_seconds)
     print(json.dumps(res), flush=True)
     return rc
@@ -377,7 +438,7 @@ def c5_workload(a):
     c2, rc2 = check_against(int(cs[-1]), fx and fx["commit_root"], "c5 commit root, tests/golden/c5.json")
     res["root_check"] = f"batch: {c1}; commit: {c2}"
     rc = rc1 or rc2
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         from oracle import oracle as o
         host = buf.cpu().numpy()
         reps, t0 = 0, time.perf_counter()
@@ -884,20 +945,21 @@ def gather_workload(a):
     # the same arena through the uniform-length path (k_xxh64_glds_skew: every block 32 KiB,
     # in slot order), 3 launches after the timed region: the rate this placement gives the
     # uniform kernel, beside which the gather's frac reads
-    ref = torch.empty(n, dtype=torch.int64, device=dev)
-    rms = []
-    for r in range(4):
-        e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-        e[0].record(stream)
-        engine.checksum_device(arena_ptr, slot, n, ref.data_ptr(), slot, 0, st)
-        e[1].record(stream)
-        torch.cuda.synchronize()
-        if r:
-            rms.append(e[0].elapsed_time(e[1]))
-    ref_gbs = n * (slot + 8) / (sum(rms) / len(rms) * 1e-3) / 1e9
-    res["roofline"]["uniform_same_arena"] = {"kernel": KERNEL, "GB/s": round(ref_gbs, 1),
-                                             "frac": round(ref_gbs / HBM_PEAK_GBS, 4)}
-    del ref
+    if a.full:
+        ref = torch.empty(n, dtype=torch.int64, device=dev)
+        rms = []
+        for r in range(4):
+            e = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+            e[0].record(stream)
+            engine.checksum_device(arena_ptr, slot, n, ref.data_ptr(), slot, 0, st)
+            e[1].record(stream)
+            torch.cuda.synchronize()
+            if r:
+                rms.append(e[0].elapsed_time(e[1]))
+        ref_gbs = n * (slot + 8) / (sum(rms) / len(rms) * 1e-3) / 1e9
+        res["roofline"]["uniform_same_arena"] = {"kernel": KERNEL, "GB/s": round(ref_gbs, 1),
+                                                 "frac": round(ref_gbs / HBM_PEAK_GBS, 4)}
+        del ref
     from storm_amd import blocks
     digest = blocks.Checksum(out.cpu().numpy().view(np.uint64).astype("<u8"))
     res["digest"] = "0x%016x" % digest
@@ -952,7 +1014,7 @@ def keytags_workload(a):
     digest = blocks.Checksum(out.cpu().numpy().view(np.uint64).astype("<u8"))
     want = fx["digest"] if fx and fx["keys"] == n else None
     res["root_check"], rc = check_against(digest, want, "f4 tag digest, tests/golden/keytags.json")
-    if not a.no_cpu:
+    if a.full and not a.no_cpu:
         from oracle import oracle as o
         m = 1 << 20
         host = keys[:m * klen].cpu().numpy()
@@ -1130,6 +1192,8 @@ def root_fixture(n_total: int, world: int, distributed: bool):
 
 def main():
     a = parse()
+    if a.dump_outputs and (a.workload != "c3" or a.in_process):
+        raise SystemExit("--dump-outputs covers the c3 / c4 workload, one process per GPU, only")
     if a.in_process:
         sys.exit(block_checksum_inprocess(a))
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1299,7 +1363,16 @@ def block_checksum_workload(a) -> int:
     # also report against a measured stream-read peak. Measured here, after
     # the timed region, on the same arena: the rate depends on where the arena lands in
     # HBM (DESIGN_LOG.md §5), so a peak from another process or box would not compare.
-    read_peak = measured_read_peak(arena_ptr, arena_n, stream, achieved)
+    read_peak = measured_read_peak(arena_ptr, arena_n, stream, achieved) if a.full else None
+
+    if a.dump_outputs:
+        # what a caller of the step receives: the shard's leaf checksums and the root
+        halves, idx = dump_checksums(cs, n_gpu, DUMP_SAMPLE // world)  # the ranks' files together keep the limit
+        tag = f"_rank{rank}" if world > 1 else ""
+        arrays = {"checksums" + tag: halves, "checksum_index" + tag: idx}
+        if rank == 0:
+            arrays["root"] = u64_halves(root_words(engine.as_tuple(root)))
+        dump_outputs(a.dump_outputs, arrays)
 
     gather = ""
     if distributed:
@@ -1307,8 +1380,10 @@ def block_checksum_workload(a) -> int:
     rc = 0
     if rank == 0:
         root_t = engine.as_tuple(root)
-        want, fx_name = root_fixture(n_total, world, distributed)
-        if want is None:
+        want, fx_name = root_fixture(n_total, world, distributed) if a.full else (None, None)
+        if not a.full:
+            check = "not checked (--full compares the root with its fixture)"
+        elif want is None:
             check = "no fixture for this workload"
         elif want == root_t:
             check = f"match ({fx_name}, tests/golden/c3c4_roots.json)"
@@ -1356,7 +1431,7 @@ def block_checksum_workload(a) -> int:
             res["config"]["process_group"] = group
             res["ranks"] = ranks
             res.update(scaling_reference(world, n_total, ranks, value, scaling))
-        if world == 1 and not a.no_cpu:
+        if a.full and world == 1 and not a.no_cpu:
             res["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
         print(json.dumps(res), flush=True)
     if distributed:
@@ -1467,7 +1542,9 @@ def block_checksum_inprocess(a) -> int:
     fx = golden("c3c4_roots.json")
     fmt = lambda r: ["0x%016x" % v for v in r[:3]] + [r[3]]  # noqa: E731
     check, rc = "no fixture for this workload", 0
-    if fx and world == 1 and n_total == fx["c3"]["n"]:
+    if not a.full:
+        check = "not checked (--full compares the roots with their fixture)"
+    elif fx and world == 1 and n_total == fx["c3"]["n"]:
         ok = fmt(rows[0]) == fx["c3"]["root"]
         check = "shard root " + ("match (c3" if ok else "MISMATCH vs c3") + ", tests/golden/c3c4_roots.json)"
         rc = 0 if ok else 3
@@ -1503,7 +1580,7 @@ def block_checksum_inprocess(a) -> int:
     }
     if world > 1:
         res.update(scaling_reference(world, n_total, ranks, value, scaling))
-    if world == 1 and not a.no_cpu:
+    if a.full and world == 1 and not a.no_cpu:
         res["cpu_baseline"] = cpu_baseline(a.cpu_seconds)
     print(json.dumps(res), flush=True)
     sync_all()

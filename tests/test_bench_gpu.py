@@ -8,9 +8,14 @@ the oracle checks in seconds:
 * Self-spawn: `bench.py --gpus 2` with no launcher; the parent starts both ranks, which
   share cuda:0 and gather over gloo (RCCL will not put two ranks on one GPU).
 
+* Plain and --full: a plain run (`--dump-outputs DIR`) leaves the CPU baseline, the read peak
+  and the fixture comparison out and writes the last step's checksums and root, which must
+  equal the oracle's; `--full` brings the extra figures back.
+
 Each printed global root must equal the oracle's for the same workload (fill seed,
 shard ranges, node addresses: storm_amd/dist.py; node format
 blocks/pointer/block.go:10-13). The 8-GPU RCCL run itself is the driver's."""
+import functools
 import json
 import os
 import socket
@@ -39,9 +44,17 @@ def _free_port():
     return port
 
 
-def _want(world):
+@functools.lru_cache(maxsize=None)
+def _leaves():
+    """The oracle's leaf checksums of the workload, computed once for the module (read-only)."""
     host = o.fill_synthetic(N_TOTAL, BLOCK, 0)
     leaf = o.checksum_batch(host, N_TOTAL, BLOCK, BLOCK, threads=8)
+    leaf.setflags(write=False)
+    return leaf
+
+
+def _want(world):
+    leaf = _leaves()
     table = [o.merkle_root(leaf[lo:hi], lo, sdist.shard_node_addr_base(N_TOTAL, lo), REV, FANOUT)
              for lo, hi in sdist.plan(N_TOTAL, world)]
     return tuple(int(v) for v in o.combine_roots(table, REV, sdist.global_root_addr(N_TOTAL), FANOUT))
@@ -103,3 +116,63 @@ def test_bench_self_spawned_two_ranks_root_matches_oracle():
     assert res["config"]["blocks_per_gpu"] == sdist.shard_range(N_TOTAL, 2, 0)[1]
     _check_group(res, 2, "gloo")
     assert _root(res) == _want(2)
+
+
+def _words(halves):
+    """float64 (high, low) 32-bit halves, as --dump-outputs writes 64-bit words, back to ints."""
+    return [(int(h) << 32) | int(lo) for h, lo in halves.tolist()]
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import numpy as np
+    out = tmp_path / "dump"
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR",
+                                                             "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--total-blocks", str(N_TOTAL),
+           "--arena", str(ARENA), "--steps", "3", "--warmup", "1", "--settle", "0", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    res = json.loads(lines[0])
+    # the headline fields, and none of what --full adds
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0
+    assert res["roofline"]["launch_ms"]["n"] == 3 * res["config"]["passes_per_step"]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype"):
+        assert k in res
+    assert "cpu_baseline" not in res and res["roofline"]["measured_read_peak"] is None
+    assert res["root_check"].startswith("not checked")
+    # the dump: every checksum (the workload is below the sample size) and the root, float64
+    files = sorted(f.name for f in out.iterdir())
+    assert files == ["checksum_index.npy", "checksums.npy", "root.npy"]
+    arrays = {f: np.load(out / f) for f in files}
+    assert all(a.dtype == np.float64 for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 << 20
+    assert arrays["checksum_index.npy"].tolist() == list(range(N_TOTAL))
+    assert arrays["checksums.npy"].shape == (N_TOTAL, 2)
+    got = np.array(_words(arrays["checksums.npy"]), dtype=np.uint64)
+    assert np.array_equal(got, _leaves())
+    want_root = o.merkle_root(_leaves(), 0, sdist.shard_node_addr_base(N_TOTAL, 0), REV, FANOUT)
+    assert tuple(_words(arrays["root.npy"])) == tuple(int(v) for v in want_root) == _root(res)
+
+
+@pytest.mark.timeout(300)
+def test_bench_full_adds_the_read_peak_and_the_fixture_check():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR",
+                                                             "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--total-blocks", str(N_TOTAL),
+           "--arena", str(ARENA), "--steps", "2", "--warmup", "1", "--settle", "0", "--full", "--cpu-seconds", "0.4"]
+    p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
+    assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
+    res = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == 2 and res["root_check"] == "no fixture for this workload"
+    peak = res["roofline"]["measured_read_peak"]
+    assert peak and peak["GB/s"] > 0
+    assert res["cpu_baseline"]["value"] > 0 and res["cpu_baseline"]["library_host_leg"]["value"] > 0
+    assert _root(res) == tuple(int(v) for v in
+                               o.merkle_root(_leaves(), 0, sdist.shard_node_addr_base(N_TOTAL, 0), REV, FANOUT))

