@@ -282,6 +282,55 @@ inline VerifyResult VerifyChecksumBatch(const void* base, size_t n, size_t strid
     return r;
 }
 
+// Scrub (stormck_scrub_device / stormck_scrub_host): walk a whole snapshot from its
+// singularity block, or one tree from an explicit root, verifying every reachable block
+// against the checksum its parent holds. A damaged store is not an exception: the report
+// says what is wrong (n_mismatch, n_structural, first_*), and ScrubResult::message is the
+// storm-format text of the first error. `device` = true: d_store is device memory and the
+// walk is queued on `stream`; false: host memory on host_threads pool threads (0 = the pool).
+// reachable (optional) gets (n_blocks+31)/32 words, in the memory the store lives in.
+struct ScrubResult {
+    stormck_scrub_report report;
+    std::string message;  // "" when the store is intact
+    bool ok() const { return report.n_mismatch + report.n_structural == 0; }
+};
+namespace detail {
+inline ScrubResult scrub_result(int rc, const stormck_scrub_report& report) {
+    if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) throw DeviceError(rc);
+    return ScrubResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
+}
+// The device workspace of one scrub call.
+struct ScrubWorkspace {
+    void* p = nullptr;
+    uint64_t bytes;
+    explicit ScrubWorkspace(uint64_t n_blocks) : bytes(stormck_scrub_workspace_bytes(n_blocks)) {
+        check(stormck_device_alloc(bytes, &p));
+    }
+    ~ScrubWorkspace() { (void)stormck_device_free(p); }
+    ScrubWorkspace(const ScrubWorkspace&) = delete;
+    ScrubWorkspace& operator=(const ScrubWorkspace&) = delete;
+};
+}  // namespace detail
+inline ScrubResult Scrub(const void* store, const stormck_scrub_layout& layout, bool device, uint32_t* reachable = nullptr,
+                         void* stream = nullptr, uint32_t host_threads = 0) {
+    stormck_scrub_report report{};
+    if (!device) return detail::scrub_result(stormck_scrub_host(store, &layout, reachable, &report, host_threads), report);
+    detail::ScrubWorkspace ws(layout.n_blocks);
+    return detail::scrub_result(stormck_scrub_device(store, &layout, ws.p, ws.bytes, reachable, &report, stream), report);
+}
+inline ScrubResult ScrubTree(const void* store, const stormck_scrub_layout& layout, const Pointer& root, BlockType root_type,
+                             uint32_t leaf_kind, uint32_t leaf_len, bool device, uint32_t* reachable = nullptr,
+                             void* stream = nullptr, uint32_t host_threads = 0) {
+    stormck_scrub_report report{};
+    const stormck_pointer* r = reinterpret_cast<const stormck_pointer*>(&root);
+    if (!device)
+        return detail::scrub_result(stormck_scrub_tree_host(store, &layout, r, root_type, leaf_kind, leaf_len, reachable,
+                                                            &report, host_threads), report);
+    detail::ScrubWorkspace ws(layout.n_blocks);
+    return detail::scrub_result(stormck_scrub_tree_device(store, &layout, r, root_type, leaf_kind, leaf_len, ws.p, ws.bytes,
+                                                          reachable, &report, stream), report);
+}
+
 // ---- block layouts -------------------------------------------------------------
 
 // pointer.Block (blocks/pointer/block.go:10-13); PointersPerBlock = 1200 (params.go:6),

@@ -480,6 +480,92 @@ int stormck_commit_split(void* arena, stormck_dirty_block* blocks, uint64_t n, u
                          uint64_t* last_allocated_block, uint64_t* out_checksums, const int* devices, int n_devices,
                          uint32_t host_threads, uint64_t device_leaves, uint64_t* device_done);
 
+/* ---- scrub: verify a whole snapshot from its singularity block ---------------
+ * In storm a block's expected checksum lives in its parent (cache/trace.go:10-42,
+ * cache/cache.go:157-162), so the integrity of a snapshot is a level-synchronous descent:
+ * the mirror image of the commit. The image holds block `a` at store + a * block_size.
+ *
+ *   singularity (address 0)  72 B hashed with Checksum (bytes 0..7) zeroed; origin of the
+ *                            space tree: SpacePointer @32, SpaceBlockType @56
+ *   pointer.Block, fanout F  (25*F+7)&~7 B; entry i = Pointers[i] @24*i, type byte @24*F+i:
+ *                            0 Free (skipped), 1 a pointer block of the same tree, 2 its leaf
+ *   spacelist.Block, S       (72*S+2+7)&~7 B; space k @72*k: KeyStorePointer @16,
+ *                            ObjectStorePointer @40, their type bytes @64 / @65, State @66;
+ *                            only spaces with State == 1 (Defined) are followed: a key tree
+ *                            with objectlist leaves and an object tree with blob leaves
+ *   objectlist / blob        objectlist_len / blob_len B, no children
+ *
+ * A reference is (parent address, slot): the pointer index in a pointer block, 2*k (key
+ * tree) or 2*k+1 (object tree) in a spacelist block, (0, 0) for the root. Its level is the
+ * referenced block's depth below the root (the root is level 0). Rules, in this order:
+ *   TYPE       a type byte above 2, or a State above 2 (reported once, at slot 2*k)
+ *   RANGE      the address is 0 or >= n_blocks (tested before any multiplication)
+ *   DUPLICATE  the address was referenced before in this scrub: at a shallower level, or at
+ *              the same level by a smaller (parent, slot)
+ *   MISMATCH   the block's checksum differs from the one its parent holds
+ * A reference that breaks a rule is never read; a block that mismatches is counted and
+ * never expanded; the walk goes on over everything reachable through verified blocks.
+ * The first error is the one at the shallowest level, and within it the smallest (parent,
+ * slot), whatever order the blocks were visited in. */
+#define STORMCK_HAS_SCRUB 1
+typedef struct stormck_scrub_layout {
+    uint64_t block_size;        /* 32768 */
+    uint64_t n_blocks;          /* addresses 0..n_blocks-1 exist in the image (at most 2^36) */
+    uint32_t pointer_fanout;    /* 1200; 10 under -tags test */
+    uint32_t spaces_per_block;  /* 400; 10 */
+    uint32_t objectlist_len;    /* 31808; 536 */
+    uint32_t blob_len;          /* 32768 */
+} stormck_scrub_layout;
+
+enum { STORMCK_SCRUB_POINTER, STORMCK_SCRUB_SPACELIST, STORMCK_SCRUB_OBJECTLIST, STORMCK_SCRUB_BLOB };
+enum { STORMCK_SCRUB_OK, STORMCK_SCRUB_MISMATCH, STORMCK_SCRUB_RANGE, STORMCK_SCRUB_TYPE, STORMCK_SCRUB_DUPLICATE };
+
+typedef struct stormck_scrub_report {
+    uint64_t verified[4];   /* blocks whose checksum matched, per kind above */
+    uint64_t bytes_hashed;  /* of every block read, the singularity's 72 included */
+    uint64_t n_mismatch;    /* referenced, in range, checksum differs: not expanded */
+    uint64_t n_structural;  /* references not followed: RANGE, TYPE, DUPLICATE */
+    uint32_t levels;        /* frontier levels hashed */
+    uint32_t first_error;   /* STORMCK_SCRUB_*; the fields below describe it */
+    uint32_t first_level, first_slot;
+    uint64_t first_parent, first_address, first_computed, first_expected; /* the last two: MISMATCH only */
+} stormck_scrub_report;
+
+/* Bytes of device workspace a scrub of n_blocks needs: 256 + 57 per block + the visited
+ * bitmap (DESIGN.md "Scrub"). Host logic. */
+uint64_t stormck_scrub_workspace_bytes(uint64_t n_blocks);
+/* Scrub the image at d_store from its singularity: the 72-byte singularity is read back and
+ * verified on the host (a failure is MISMATCH at address 0, and nothing else is walked), then
+ * the space tree, its spacelist leaves and every Defined space's two trees are walked on the
+ * device, one frontier level per step: the level is hashed by the batch dispatch
+ * (stormck_checksum_gather_device's), then k_scrub_expand compares, validates and builds the
+ * next level. d_store and d_workspace are 8-byte aligned, block_size a multiple of 8.
+ * d_reachable (optional): (n_blocks+31)/32 words; bit a is set iff block a was referenced,
+ * in range and referenced for the first time (read, whether or not it then matched); bit 0
+ * is always set, so popcount = 1 + sum(verified) + n_mismatch (a singularity that fails is
+ * bit 0 itself). Synchronous: queues its work on `stream` behind what is already there and
+ * returns when the walk has finished. Returns STORMCK_EMISMATCH if n_mismatch +
+ * n_structural > 0, with the report filled and the first error's text in
+ * stormck_last_error(); STORMCK_EINVAL for null pointers, a zero fanout, lengths above
+ * block_size, a small workspace or a stream that is being captured. */
+int stormck_scrub_device(const void* d_store, const stormck_scrub_layout* layout, void* d_workspace,
+                         uint64_t workspace_bytes, uint32_t* d_reachable, stormck_scrub_report* report, void* stream);
+/* One tree from an explicit root of type root_type (Free: nothing to walk). leaf_kind: the
+ * kind of its leaves (STORMCK_SCRUB_SPACELIST / _OBJECTLIST / _BLOB; spacelist leaves are
+ * expanded); leaf_len overrides the layout's length for that kind (0: the layout's), so shard
+ * trees and test trees of any leaf size can be scrubbed. */
+int stormck_scrub_tree_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                              uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, void* d_workspace,
+                              uint64_t workspace_bytes, uint32_t* d_reachable, stormck_scrub_report* report, void* stream);
+/* The same walks over an image in host memory (storm's stores are host memory or files), each
+ * level hashed on host_threads library pool threads (0 = the pool). Same rules, report, bitmap
+ * and return codes; needs no device and is not routed. */
+int stormck_scrub_host(const void* store, const stormck_scrub_layout* layout, uint32_t* reachable,
+                       stormck_scrub_report* report, uint32_t host_threads);
+int stormck_scrub_tree_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                            uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, uint32_t* reachable,
+                            stormck_scrub_report* report, uint32_t host_threads);
+
 /* ---- synthetic data (benchmarks / tests) -----------------------------------
  * Word w of block i = splitmix64(seed ^ (((first + i) << 20) + w)), w < stride/8,
  * little-endian. stride % 16 == 0, d_dst 16-byte aligned. */

@@ -8,6 +8,7 @@ from them, and per-shard roots gathered over RCCL. Submodules:
 * ``layouts``  — storm block structs (pointer, blob, objectlist, spacelist, singularity)
 * ``engine``   — device-resident entry points (raw pointers / torch tensors)
 * ``commit``   — f1: level-synchronous Cache.Commit of a dirty forest (stormck_commit_device)
+* ``scrub``    — walk a whole snapshot from its singularity and verify every reachable block
 * ``dist``     — shard planning and the root all-gather
 * ``build``    — in-tree hipcc build of libstormck.so
 """

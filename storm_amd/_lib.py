@@ -74,6 +74,22 @@ class ShardStruct(ctypes.Structure):
                 ("device", ctypes.c_int32), ("len", c_uint32)]
 
 
+class ScrubLayoutStruct(ctypes.Structure):
+    """stormck_scrub_layout: the image and block sizes a scrub walks with."""
+
+    _fields_ = [("block_size", c_uint64), ("n_blocks", c_uint64), ("pointer_fanout", c_uint32),
+                ("spaces_per_block", c_uint32), ("objectlist_len", c_uint32), ("blob_len", c_uint32)]
+
+
+class ScrubReportStruct(ctypes.Structure):
+    """stormck_scrub_report."""
+
+    _fields_ = [("verified", c_uint64 * 4), ("bytes_hashed", c_uint64), ("n_mismatch", c_uint64),
+                ("n_structural", c_uint64), ("levels", c_uint32), ("first_error", c_uint32),
+                ("first_level", c_uint32), ("first_slot", c_uint32), ("first_parent", c_uint64),
+                ("first_address", c_uint64), ("first_computed", c_uint64), ("first_expected", c_uint64)]
+
+
 # name -> (restype, argtypes); mirrors include/stormck.h one to one.
 SIGNATURES = {
     "stormck_abi_version": (c_int, []),
@@ -144,6 +160,17 @@ SIGNATURES = {
     "stormck_commit_split": (
         c_int, [c_void_p, c_void_p, c_uint64, c_uint64, POINTER(c_uint64), c_void_p, c_void_p, c_int, c_uint32,
                 c_uint64, POINTER(c_uint64)]),
+    "stormck_scrub_workspace_bytes": (c_uint64, [c_uint64]),
+    "stormck_scrub_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_void_p, c_uint64, c_void_p, POINTER(ScrubReportStruct), c_void_p]),
+    "stormck_scrub_tree_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_uint32, c_uint32, c_void_p,
+                c_uint64, c_void_p, POINTER(ScrubReportStruct), c_void_p]),
+    "stormck_scrub_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_void_p, POINTER(ScrubReportStruct), c_uint32]),
+    "stormck_scrub_tree_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_uint32, c_uint32, c_void_p,
+                POINTER(ScrubReportStruct), c_uint32]),
     "stormck_fill_synthetic_device": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p]),
 }
 

@@ -1467,6 +1467,7 @@ int host_pipeline_multi(const void* base, uint64_t stride, const uint32_t* lens,
 }
 
 #include "multi_root.h"
+#include "scrub.h"
 
 }  // namespace
 
@@ -3966,6 +3967,31 @@ int stormck_route_plan_commit(const stormck_dirty_block* blocks, uint64_t n, uin
     *leg = n ? p.leg : STORMCK_LEG_NONE;
     if (predicted_us) std::memcpy(predicted_us, p.us, sizeof p.us);
     return STORMCK_OK;
+}
+
+uint64_t stormck_scrub_workspace_bytes(uint64_t n_blocks) { return scrub_workspace_bytes(n_blocks); }
+
+int stormck_scrub_device(const void* d_store, const stormck_scrub_layout* layout, void* d_workspace,
+                         uint64_t workspace_bytes, uint32_t* d_reachable, stormck_scrub_report* report, void* stream) {
+    return scrub_device(d_store, layout, d_workspace, workspace_bytes, d_reachable, report, stream);
+}
+
+int stormck_scrub_tree_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                              uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, void* d_workspace,
+                              uint64_t workspace_bytes, uint32_t* d_reachable, stormck_scrub_report* report, void* stream) {
+    return scrub_tree_device(d_store, layout, root, root_type, leaf_kind, leaf_len, d_workspace, workspace_bytes,
+                             d_reachable, report, stream);
+}
+
+int stormck_scrub_host(const void* store, const stormck_scrub_layout* layout, uint32_t* reachable,
+                       stormck_scrub_report* report, uint32_t host_threads) {
+    return scrub_host(store, layout, reachable, report, host_threads);
+}
+
+int stormck_scrub_tree_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                            uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, uint32_t* reachable,
+                            stormck_scrub_report* report, uint32_t host_threads) {
+    return scrub_tree_host(store, layout, root, root_type, leaf_kind, leaf_len, reachable, report, host_threads);
 }
 
 int stormck_fill_synthetic_device(void* d_dst, uint64_t stride, uint64_t n, uint64_t first, uint64_t seed,
