@@ -35,7 +35,7 @@ def _newer(target: str, sources) -> bool:
 
 
 # the sources libstormck.so is compiled from (its build id hashes them)
-SOURCES = [os.path.join(CSRC, f) for f in ("stormck.hip", "kernels.h", "multi_root.h", "scrub.h", "xxh64_dev.h", "xxh64_host.h")] + \
+SOURCES = [os.path.join(CSRC, f) for f in ("stormck.hip", "dispatch.h", "kernels.h", "multi_root.h", "scrub.h", "xxh64_dev.h", "xxh64_host.h")] + \
     [os.path.join(ROOT, "include", "stormck.h")]
 
 
@@ -68,8 +68,8 @@ def build_lib(force: bool = False) -> str:
 
 
 # The probe build: the same sources with -DSTORMCK_PROBES, i.e. with the variants measured
-# and rejected in DESIGN.md and the environment knobs that select them (stormck.hip
-# STORMCK_KNOB). Design tools and tests/test_probe_build.py load it; the product does not.
+# and rejected in DESIGN.md and the environment knobs that select them (dispatch.h
+# Knobs). Design tools and tests/test_probe_build.py load it; the product does not.
 PROBES_LIB = os.path.join(ROOT, "tools", "libstormck_probes.so")
 
 

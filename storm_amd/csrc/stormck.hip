@@ -30,6 +30,7 @@
 #include <rccl/rccl.h>  // types and declarations only: RCCL is loaded at run time (multi_root.h)
 
 #include "../../include/stormck.h"
+#include "dispatch.h"
 #include "kernels.h"
 #include "xxh64_host.h"
 
@@ -198,58 +199,9 @@ int fail(int code, const std::string& msg) {
                         std::string(#expr) + ": " + hipGetErrorString(e_));                        \
     } while (0)
 
-// Stripe-loop unroll of the general quad kernel: 16 x 8-byte loads in flight per
-// lane per pipelined group (design probe, profiles/r01_probe.txt: U=16 with plain
-// loads is the fastest quad variant; non-temporal loads cost 35%).
-constexpr int kU = 16;
-constexpr int kQuadSpreadDepth = 4;  // groups of kU loads in flight, one-wave quad workgroups
-// LDS-staged fast path: 8-wave (512-thread) workgroups of 128 blocks, tiles of 16
-// stripes (512 B per block, 64 KiB per tile), a ring of 2 tiles (128 KiB LDS, one
-// workgroup per CU), non-temporal LDS-DMA (aux = 2). Measured best of the swept
-// waves x tile x ring grid (profiles/r01_probe_8wave.txt: 0.886 of 8 TB/s median vs
-// 0.840 for 4 waves / 3 x 32 KiB); 16 stripes divide storm's 32 KiB blocks.
-constexpr int kTileStripes = 16;
-constexpr int kRing = 2;
-constexpr int kGldsWaves = 8;
-constexpr unsigned kGldsThreads = 64 * kGldsWaves;
-constexpr unsigned kGldsBlocks = 16 * kGldsWaves;
-constexpr int kAuxNT = 2;
-constexpr uint64_t kMultiBpw = 5;          // blocks per workgroup of k_xxh64_wide_multi
-constexpr uint64_t kMultiBpwRing = 8;      // ring staging, batches above kMultiBpw per CU (133 KiB of LDS)
-constexpr uint64_t kMultiBpwWide = 16;     // ring staging in 2 KiB chunks, batches above 8 per CU (133 KiB)
-[[maybe_unused]] constexpr uint32_t kChunkPiecesWide = 128;  // the 2 KiB chunk of kMultiBpwWide (probe build)
-constexpr uint64_t kWideBatch = 128;      // batches up to this many blocks: k_xxh64_wide
-constexpr uint64_t kCommitWide = 256;     // f1 levels up to this many blocks: k_commit_level_wide
-constexpr uint64_t kStreamBatch = 16384;  // f1 commit levels from this many blocks: k_commit_level_glds
-constexpr uint64_t kCommitOnePiece = 4096; // f1 commits with at most this many leaves: one checksum copy-back
-// Uniform batches take the LDS-staged kernel from kMidBatch blocks. Below kBigBatch its
-// workgroups are 2 waves (32 blocks, 16 KiB of ring) rather than 8 (128 blocks, 128 KiB):
-// 16,384 blocks in 8-wave workgroups fill only 128 of the 256 CUs
-// (profiles/r01_chain/mid_sweep.txt: 16,384 blocks in 84 us instead of 110; 12,288 in 67
-// instead of the register quad's 76).
-constexpr uint64_t kMidBatch = 10240;
-constexpr uint64_t kBigW = 131072;  // uniform batches below this many blocks choose their workgroup size
-constexpr uint64_t kBigBatch = 24576;
-constexpr int kMidWaves = 2;
-constexpr unsigned kThreads = 256;
-constexpr uint32_t kMaxFanout = 1u << 16;
-// Merkle levels of at most this many nodes take one workgroup per node (k_pointer_level_wide):
-// a node is then about one XXH64 chain (~26 us for 30,000 B); larger levels put a quad
-// on each node, 64 nodes per workgroup, to keep every CU busy.
-constexpr uint64_t kWideNodes = 256;
-// k_pointer_level_pc: tiles of 15 stripes (20 child slots) per node; the producer wave
-// loads child checksums 6 tiles (90 chain rounds) ahead of the tile it writes
-// (profiles/r02_merkle/: 38 us for 13,982 nodes against 41 at 4 tiles and 52 at 12).
-constexpr uint32_t kRingTile = 15;
-constexpr int kRingPrefetch = 6;
-
-// Skewed persistent streaming kernel (k_xxh64_glds_skew): wave v starts kSkewTiles*v
-// tiles late, 4 KiB apart at 16-stripe tiles (profiles/r01_probe_phase_skew.txt). Its
-// first and last 7*kSkewTiles steps leave waves idle, so it runs only when every
-// workgroup has at least kSkewMinSteps tile steps (idle share <= 1.6%): for 32 KiB
-// blocks, batches of about 1.8M blocks and up (the bench's 4M-block passes).
-constexpr int kSkewTiles = 8;
-constexpr uint64_t kSkewMinSteps = 3584;
+static_assert(kPlanRingSlots == kRingSlots && kPlanPipePieces == uint64_t{kPipeMaxChunks} * kChunkPieces &&
+                  kPlanMultiPieces == kMultiPieces && kPlanOrderBuckets == kOrderBuckets && kPlanNodeLds == kNodeLds,
+              "dispatch.h plans with the limits of kernels.h");
 
 // Cached answer to "is there a usable gfx950 device?" per process.
 int device_check() {
@@ -431,53 +383,54 @@ uint32_t debug_stall(hipStream_t st) {
     return (only == 0 || reinterpret_cast<uintptr_t>(st) == only) ? c : 0u;
 }
 
-// Probe knobs. The shipped library has one dispatch, fixed at compile time. The variants
-// measured and rejected in DESIGN.md, and the environment switches that select them, are
-// compiled only into the probe build (-DSTORMCK_PROBES: tools/libstormck_probes.so, which
-// the design tools and tests/test_probe_build.py load). In this build every
-// STORMCK_KNOB(...) is null, so each switch folds to its default and the rejected
-// kernels are not instantiated.
-#ifdef STORMCK_PROBES
-#define STORMCK_KNOB(NAME) std::getenv(NAME)
-#else
-#define STORMCK_KNOB(NAME) (static_cast<const char*>(nullptr))
-#endif
-
-// Ring depth of the pipelined staging in the wide-multi kernels (kernels.h
-// multi_stage_hash_pipe): kRingSlots; probe knob STORMCK_STAGE_PIPE=0 stages whole blocks
-// first (A/B). 6- and 7-slot rings were measured slower (DESIGN_LOG.md §5).
-uint32_t pipe_staging() {
-    static const uint32_t slots = [] {
-        const char* e = STORMCK_KNOB("STORMCK_STAGE_PIPE");
-        return (e && e[0] == '0') ? 0u : kRingSlots;
-    }();
-    return slots;
+// Runtime choices as compile-time constants, so that each kernel family's launch is written
+// once, in a generic lambda: with_consts(f, a, b) calls f(std::bool_constant<a>{},
+// std::bool_constant<b>{}); with_int<1, 3, 8>(w, f) calls f(std::integral_constant<int, w>{})
+// for a listed w. A lambda excludes with `if constexpr` the combinations no plan asks for
+// (dispatch.h), so they are not instantiated: the variants of the probe build among them.
+#define STORMCK_V(C) decltype(C)::value
+template <class F>
+void with_consts(F&& f) { f(); }
+template <class F, class... Rest>
+void with_consts(F&& f, bool b, Rest... rest) {
+    if (b) with_consts([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+    else with_consts([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+template <int... Vs, class F>
+void with_int(int v, F&& f) {
+    (void)((v == Vs && (f(std::integral_constant<int, Vs>{}), true)) || ...);
 }
 
-// 16 blocks per workgroup (one full chain wave) through 4-slot rings of 2 KiB chunks with
-// double-buffered stagers, for batches of 9..16 blocks per CU: measured no faster than
-// the register-quad kernel (2,049 / 3,072 / 4,096 blocks of 31,808 B: 33.2 / 35.3 / 38.1
-// against 34.7 / 35.0 / 35.1 us in a round-3 probe; two 8-block rings per CU lost the same
-// way, profiles/r03_multi16/), so off; probe knob STORMCK_WIDE16=1.
-bool wide16_on() {
-    static const bool on = [] {
-        const char* e = STORMCK_KNOB("STORMCK_WIDE16");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
-// Blocks per workgroup of the wide-multi kernels for a batch of n on ncu CUs: kMultiBpw
-// up to kMultiBpw per CU; with ring staging, kMultiBpwRing up to that many per CU. One
-// wave walks all of a workgroup's chains, so 8 cost about what 5 do (1,600 / 2,048 blocks:
-// 24.2 / 25.4 us against 34.5 / 34.8 on the quad kernel); at or below 5 per CU the
-// 5-block workgroups are about 1 us faster (profiles/r02_pipe/bpw_ab/). 0: not this kernel.
-uint64_t multi_bpw(uint64_t n, uint64_t ncu) {
-    if (ncu == 0) return 0;
-    if (n <= kMultiBpw * ncu) return kMultiBpw;
-    if (pipe_staging() && n <= kMultiBpwRing * ncu) return kMultiBpwRing;
-    if (pipe_staging() && n <= kMultiBpwWide * ncu && wide16_on()) return kMultiBpwWide;  // probe knob only
-    return 0;
+// The wide-multi launch of a checksum batch and of a commit level: the fault slot of the
+// launch's stream, the debug stall, and the workgroup shape as constants.
+// launch(BPW, RING, CHUNK, DBL, fault, stall) launches the caller's kernel.
+template <class F>
+int launch_wide_multi(const MultiShape& s, hipStream_t st, F&& launch) {
+    uint32_t* fault = nullptr;  // the fault slot of this launch's stream
+    if (s.ring) {
+        const int frc = fault_slot(st, &fault);
+        if (frc) return frc;
+    }
+    const uint32_t stall = debug_stall(st);
+    auto shape = [&](auto BPW, auto RING) {
+        constexpr bool wide = STORMCK_V(BPW) == kMultiBpwWide;
+        launch(BPW, RING, std::integral_constant<uint32_t, wide ? kChunkPiecesWide : kChunkPieces>{},
+               std::bool_constant<wide>{}, fault, stall);
+    };
+    using Ring = std::integral_constant<uint32_t, kRingSlots>;
+    if constexpr (kProbes) {  // the rejected 16-block / whole-block-staging variants
+        if (s.ring && s.bpw == kMultiBpwWide) {
+            shape(std::integral_constant<int, kMultiBpwWide>{}, Ring{});
+            return STORMCK_OK;
+        }
+        if (!s.ring) {
+            shape(std::integral_constant<int, kMultiBpw>{}, std::integral_constant<uint32_t, 0>{});
+            return STORMCK_OK;
+        }
+    }
+    if (s.bpw == kMultiBpw) shape(std::integral_constant<int, kMultiBpw>{}, Ring{});
+    else shape(std::integral_constant<int, kMultiBpwRing>{}, Ring{});
+    return STORMCK_OK;
 }
 
 // Stream-ordered workspaces (the gather order) come from a private pool per device that
@@ -507,495 +460,136 @@ int workspace_pool(hipMemPool_t* out) {
     return STORMCK_OK;
 }
 
-// Per-block-length and gathered batches whose longest block is at most this many bytes
-// stay on the register quad kernel: k_xxh64_glds_var streams 512-byte rows in lock step,
-// and short blocks leave most of a step's rows empty (storm's `-tags test` sizes 256 / 536
-// / 728 B: 3.7 against 6.4 G blocks/s strided, 2.8 against 6.2 shuffled, 1M blocks).
-// One length L per batch, strided, var / quad in G blocks/s: 1 KiB 4.29 / 5.73, 2 KiB
-// 2.82 / 2.99, 4 KiB 1.56 / 1.59, 8 KiB 0.85 / 0.76, 16 KiB 0.41 / 0.37 (DESIGN_LOG.md §5
-// "Short blocks", profiles/r04_small_blocks/, r04_small_crossover/).
-constexpr uint64_t kVarMinLen = 4096;
-uint64_t var_min_len() {  // probe knob STORMCK_VAR_MIN_LEN: another threshold (A/B)
-    static const uint64_t v = [] {
-        const char* e = STORMCK_KNOB("STORMCK_VAR_MIN_LEN");
-        return e ? std::strtoull(e, nullptr, 10) : kVarMinLen;
-    }();
-    return v;
-}
-
-// Gathers of at least this many blocks visit them in a locality order (k_order_*); probe
-// knob STORMCK_GATHER_ORDER=0 turns it off (A/B).
-constexpr uint64_t kOrderMinBlocks = 1u << 20;
-bool order_on() {
-    static const bool on = [] {
-        const char* e = STORMCK_KNOB("STORMCK_GATHER_ORDER");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// Probe knob STORMCK_GATHER_RANK=1: large gathers with per-block lengths deal each group's
-// rows by length rank (k_order_rank; measured slower, DESIGN_LOG.md §10).
-[[maybe_unused]] bool rank_on() {
-    static const bool on = [] {
-        const char* e = STORMCK_KNOB("STORMCK_GATHER_RANK");
-        return e && e[0] == '1';
-    }();
-    return on;
-}
-
-bool grid_for(uint64_t threads, dim3* grid) {
-    const uint64_t blocks = (threads + kThreads - 1) / kThreads;
-    if (blocks == 0 || blocks > 0x7fffffffULL) return false;
-    *grid = dim3(static_cast<unsigned>(blocks));
-    return true;
-}
-
-bool big_w_on() {  // probe knob STORMCK_BIG_W=0: batches from kBigBatch on always take 8-wave workgroups
-    static const bool on = [] {
-        const char* e = STORMCK_KNOB("STORMCK_BIG_W");
-        return !(e && e[0] == '0');
-    }();
-    return on;
-}
-
-// remote: the blocks are host memory read in place over PCIe (the split leg). The link
-// carries a kernel's loads as read requests of the loads' size, so the kernels that read
-// 16 bytes per lane in wave-wide runs (LDS-DMA) keep it at its rate, while the register
-// quad kernel's 32-byte reads run it at ~36 GB/s against ~54 (profiles/r05_rates/):
-// gathers past the wide-multi range then take the LDS-DMA var kernel at any size.
+// One batch on stream `st`: the plan is plan_checksum's (dispatch.h, with the measurements
+// behind every threshold). remote: the blocks are host memory read in place over PCIe.
 int launch_checksum(const uint8_t* base, uint64_t stride, const uint32_t* lens, uint32_t len, const uint64_t* offs,
                     uint64_t n, uint64_t* out, const uint64_t* expected, unsigned long long* first_bad,
                     unsigned long long* n_bad, hipStream_t st, bool remote = false) {
-    const bool verify = expected != nullptr;
-    // The longest block the dispatch plans for: len for uniform lengths; with per-block
-    // lengths (on the device) the caller's upper bound passed in len, 0 = unknown, planned
-    // as storm's 32 KiB. Results never depend on it, only the kernel choice does.
-    const uint64_t plan_len = lens ? (len ? len : uint64_t{32768}) : len;
-    // Batch-size dispatch (profiles/r01_probe_small.txt, us per launch at 32 KiB):
-    //  * n <= kWideBatch: one workgroup per block, whole block staged in one round trip
-    //  * n <  kMidBatch: register quad kernel (64 blocks per workgroup spread the
-    //    batch over the chip; the streaming kernel's 128-block workgroups would occupy
-    //    fewer than half of the CUs)
-    //  * otherwise, uniform length, 16-byte aligned blocks at a fixed stride, at least
-    //    one LDS tile per block: LDS-staged streaming kernel (global_load_lds, nt), in
-    //    2-wave workgroups below kBigBatch; its persistent 4 KiB-skewed form when the
-    //    batch gives every CU thousands of tiles
-    if (n <= kWideBatch) {
-#define STORMCK_WIDE(LENS, OFFS, VER)                                                                           \
-    hipLaunchKernelGGL((k_xxh64_wide<LENS, OFFS, VER>), dim3(static_cast<unsigned>(n)), dim3(kThreads), 0, st, base, \
-                       stride, lens, len, offs, n, out, expected, first_bad, n_bad)
-        if (!verify) {
-            if (lens && offs) STORMCK_WIDE(true, true, false);
-            else if (lens) STORMCK_WIDE(true, false, false);
-            else if (offs) STORMCK_WIDE(false, true, false);
-            else STORMCK_WIDE(false, false, false);
-        } else {
-            if (lens && offs) STORMCK_WIDE(true, true, true);
-            else if (lens) STORMCK_WIDE(true, false, true);
-            else if (offs) STORMCK_WIDE(false, true, true);
-            else STORMCK_WIDE(false, false, true);
+    const Query q{n, len, lens != nullptr, offs != nullptr, expected != nullptr, remote,
+                  static_cast<unsigned>(reinterpret_cast<uintptr_t>(base) & 15), stride};
+    const Plan p = plan_checksum(q, cu_count(), knobs());
+    const dim3 grid(p.grid), block(p.block);
+    switch (p.kernel) {
+        case Kernel::TooLarge:
+            return fail(STORMCK_EINVAL, "batch too large for one launch");
+        case Kernel::Wide:
+            with_consts([&](auto LENS, auto OFFS, auto VER) {
+                hipLaunchKernelGGL((k_xxh64_wide<STORMCK_V(LENS), STORMCK_V(OFFS), STORMCK_V(VER)>), grid, block, 0, st,
+                                   base, stride, lens, len, offs, n, out, expected, first_bad, n_bad);
+            }, q.lens, q.offs, q.verify);
+            break;
+        case Kernel::WideMulti: {
+            const int rc = launch_wide_multi(p.multi, st, [&](auto BPW, auto RING, auto CHUNK, auto DBL, uint32_t* fault,
+                                                              uint32_t stall) {
+                with_consts([&](auto LENS, auto OFFS, auto VER) {
+                    hipLaunchKernelGGL((k_xxh64_wide_multi<STORMCK_V(LENS), STORMCK_V(OFFS), STORMCK_V(VER), STORMCK_V(BPW),
+                                                           STORMCK_V(RING), STORMCK_V(CHUNK), STORMCK_V(DBL)>),
+                                       grid, block, 0, st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad,
+                                       fault, stall);
+                }, q.lens, q.offs, q.verify);
+            });
+            if (rc) return rc;
+            break;
         }
-#undef STORMCK_WIDE
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
-    }
-    // up to 5 blocks per CU (8 with ring staging): k_xxh64_wide_multi, one workgroup per
-    // CU staging 5 (8) premultiplied blocks (the c5 commit batch is one such launch)
-    static const bool multi_on = [] {
-        const char* e = STORMCK_KNOB("STORMCK_WIDE_MULTI");  // probe knob: "0" disables
-        return !(e && e[0] == '0');
-    }();
-    const uint32_t ring_slots = pipe_staging();
-    // a uniform batch takes it when its blocks can be staged (pipelined: covers up to 64 KiB)
-    const uint64_t multi_pieces = ring_slots ? uint64_t{kPipeMaxChunks} * kChunkPieces : kMultiPieces;
-    const uint64_t ncu = cu_count();
-    const uint64_t bpw = multi_bpw(n, ncu);
-    if (multi_on && bpw > 0 &&
-        (offs || lens ||
-         ((reinterpret_cast<uintptr_t>(base) & 7) == 0 && (stride & 7) == 0 &&
-          ((reinterpret_cast<uintptr_t>(base) & 15) + len + 15) / 16 <= multi_pieces))) {
-        const dim3 grid(static_cast<unsigned>((n + bpw - 1) / bpw));
-        uint32_t* fault = nullptr;  // the fault slot of this launch's stream
-        if (ring_slots) {
-            const int frc = fault_slot(st, &fault);
-            if (frc) return frc;
-        }
-        const uint32_t stall = debug_stall(st);
-#ifdef STORMCK_PROBES  // the rejected 16-block / whole-block-staging variants
-#define STORMCK_MULTI_PROBES(LENS, OFFS, VER)                                                                  \
-        if (ring_slots && bpw == kMultiBpwWide)                                                               \
-            hipLaunchKernelGGL((k_xxh64_wide_multi<LENS, OFFS, VER, kMultiBpwWide, kRingSlots, kChunkPiecesWide, true>), \
-                               grid, dim3(kThreads), 0, st, base, stride, lens, len, offs, n, out, expected,   \
-                               first_bad, n_bad, fault, stall);                                               \
-        else if (!ring_slots)                                                                                 \
-            hipLaunchKernelGGL((k_xxh64_wide_multi<LENS, OFFS, VER, kMultiBpw, 0>), grid, dim3(kThreads), 0,    \
-                               st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad, fault, stall); \
-        else
-#else
-#define STORMCK_MULTI_PROBES(LENS, OFFS, VER)
-#endif
-#define STORMCK_MULTI(LENS, OFFS, VER)                                                                         \
-    do {                                                                                                      \
-        STORMCK_MULTI_PROBES(LENS, OFFS, VER)                                                                 \
-        if (bpw == kMultiBpw)                                                                                 \
-            hipLaunchKernelGGL((k_xxh64_wide_multi<LENS, OFFS, VER, kMultiBpw, kRingSlots>), grid, dim3(kThreads), \
-                               0, st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad, fault, stall); \
-        else                                                                                                  \
-            hipLaunchKernelGGL((k_xxh64_wide_multi<LENS, OFFS, VER, kMultiBpwRing, kRingSlots>), grid, dim3(kThreads), \
-                               0, st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad, fault, stall); \
-    } while (0)
-        if (!verify) {
-            if (lens && offs) STORMCK_MULTI(true, true, false);
-            else if (lens) STORMCK_MULTI(true, false, false);
-            else if (offs) STORMCK_MULTI(false, true, false);
-            else STORMCK_MULTI(false, false, false);
-        } else {
-            if (lens && offs) STORMCK_MULTI(true, true, true);
-            else if (lens) STORMCK_MULTI(true, false, true);
-            else if (offs) STORMCK_MULTI(false, true, true);
-            else STORMCK_MULTI(false, false, true);
-        }
-#undef STORMCK_MULTI
-#undef STORMCK_MULTI_PROBES
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
-    }
-    // Per-block lengths and/or gathered offsets (storm's dirty slots with mixed Sizeof(T)):
-    // the LDS-DMA ring with per-wave tile counts, k_xxh64_glds_var, in the same
-    // workgroup shapes as the uniform path below. base + stride batches need 16-byte
-    // aligned rows (else the quad kernel); gathered blocks are checked per block in the
-    // kernel, which hashes an unaligned one from global memory. Probe knob
-    // STORMCK_GLDS_VAR=0 restores the quad kernel (A/B).
-    static const bool var_on = [] {
-        const char* e = STORMCK_KNOB("STORMCK_GLDS_VAR");
-        return !(e && e[0] == '0');
-    }();
-    // From 44 blocks per CU (11,264 on 256 CUs): storm-mix batches in us, var kernel /
-    // register quad: 9,216 69.5 / 53.4, 10,240 70.0 / 62.9, 12,288 71.8 / 79.9, 16,384
-    // 82.1 / 124, 49,152 238 / 299 (profiles/r03_mid/varlo*, varhi*). Probe knob
-    // STORMCK_VAR_LO: the smallest batch for the var kernel.
-    static const uint64_t var_lo = [] {
-        const char* e = STORMCK_KNOB("STORMCK_VAR_LO");
-        return e ? std::strtoull(e, nullptr, 10) : 0;
-    }();
-    const uint64_t var_min_n = var_lo ? var_lo : remote ? 0 : std::max<uint64_t>(kMidBatch, 44 * cu_count());
-    if (var_on && n >= var_min_n && n > (remote ? kMultiBpwRing : 16) * cu_count() &&
-        (lens || offs) && plan_len > var_min_len() &&
-        (offs || ((reinterpret_cast<uintptr_t>(base) & 15) == 0 && (stride & 15) == 0))) {
-        // below kBigBatch: 3- or 1-wave workgroups, whichever loads the busiest CU least;
-        // up to kBigW, 3-wave workgroups where they cut the busiest CU's blocks by a
-        // quarter against 8-wave ones (as the uniform path below)
-        const uint64_t ncu_v = cu_count() ? cu_count() : 256;
-        auto busiest = [&](uint64_t w) { return (((n + 16 * w - 1) / (16 * w)) + ncu_v - 1) / ncu_v * 16 * w; };
-        const bool big3 = n >= kBigBatch && n < kBigW && big_w_on() && 4 * busiest(3) <= 3 * busiest(8);
-        const bool big = n >= kBigBatch && !big3;
-        static const bool var_before = [] {  // probe knob STORMCK_MID_WAVES=5: 2-wave workgroups (A/B)
-            const char* e = STORMCK_KNOB("STORMCK_MID_WAVES");
-            return e && e[0] == '5';
-        }();
-        const int vw = var_before ? 2 : (big3 || busiest(3) <= busiest(1)) ? 3 : 1;
-        const uint64_t per_wg = big ? kGldsBlocks : 16 * static_cast<uint64_t>(vw);
-        const uint64_t wgs = (n + per_wg - 1) / per_wg;
-        if (wgs > 0x7fffffffULL) return fail(STORMCK_EINVAL, "batch too large for one launch");
-        const uint64_t cus = cu_count();
-        // tile steps per workgroup, from the planning length
-        const uint64_t tiles = (plan_len / 32 + kTileStripes - 1) / kTileStripes;
-        const bool persistent = big && cus > 0 && wgs >= cus && (wgs + cus - 1) / cus * tiles >= kSkewMinSteps;
-        const dim3 grid(static_cast<unsigned>(persistent ? cus : wgs));
-        // large gathers visit their blocks in a locality order (kernels.h k_order_*): a
-        // stream-ordered workspace from the library's own pool (the count matrix, the
-        // order, the offsets and lengths in that order: 16 bytes per block), freed on the
-        // stream after the launch
-        if (offs && !verify && big && n >= kOrderMinBlocks && n < (uint64_t{1} << 32) && order_on()) {
+        case Kernel::GldsVar:  // 2-wave workgroups: the probe build's kernels before round 3
+            with_int<1, 2, 3, kGldsWaves>(p.waves, [&](auto W) {
+                with_consts([&](auto VER, auto SKEW, auto LENS, auto OFFS) {
+                    constexpr int w = STORMCK_V(W);
+                    if constexpr ((STORMCK_V(LENS) || STORMCK_V(OFFS)) && (kProbes || w != 2) &&
+                                  (!STORMCK_V(SKEW) || w == kGldsWaves))
+                        hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, STORMCK_V(VER), w,
+                                                             STORMCK_V(SKEW) ? kSkewTiles : 0, STORMCK_V(LENS), STORMCK_V(OFFS)>),
+                                           grid, block, 0, st, base, stride, lens, len, offs, n, out, expected, first_bad,
+                                           n_bad, nullptr);
+                }, q.verify, p.persistent, q.lens, q.offs);
+            });
+            break;
+        case Kernel::GldsVarOrdered: {
             hipMemPool_t pool = nullptr;
             const int prc = workspace_pool(&pool);
             if (prc) return prc;
-            // probe knob STORMCK_GATHER_DEFER=1: hash into the sorted positions (coalesced
-            // stores), then one scatter pass to the caller's indices (A/B)
-            static const bool defer = [] {
-                const char* e = STORMCK_KNOB("STORMCK_GATHER_DEFER");
-                return e && e[0] == '1';
-            }();
             const uint64_t words = (uint64_t{kOrderBuckets} * 3 + n + 1) & ~uint64_t{1};
             void* ws = nullptr;
-            HIP_TRY(hipMallocFromPoolAsync(&ws, words * 4 + n * 8 + (lens ? n * 4 : 0) + (defer ? n * 8 + 8 : 0), pool, st));
+            HIP_TRY(hipMallocFromPoolAsync(&ws, p.ws_bytes, pool, st));
             uint32_t* bounds = static_cast<uint32_t*>(ws);  // [first, end) per bucket (end: totals first)
             uint32_t* cursor = bounds + 2 * kOrderBuckets;
             uint32_t* order = cursor + kOrderBuckets;
             uint64_t* s_offs = reinterpret_cast<uint64_t*>(bounds + words);
             uint32_t* s_lens = lens ? reinterpret_cast<uint32_t*>(s_offs + n) : nullptr;
-            uint64_t* s_out = defer ? reinterpret_cast<uint64_t*>(  // 8-byte aligned after the lengths
-                                          (reinterpret_cast<uintptr_t>(s_offs + n) + (lens ? n * 4 : 0) + 7) & ~uintptr_t{7})
-                                    : nullptr;
+            uint64_t* s_out = p.defer ? reinterpret_cast<uint64_t*>(  // 8-byte aligned after the lengths
+                                            (reinterpret_cast<uintptr_t>(s_offs + n) + (lens ? n * 4 : 0) + 7) & ~uintptr_t{7})
+                                      : nullptr;
             HIP_TRY(hipMemsetAsync(bounds + kOrderBuckets, 0, kOrderBuckets * 4, st));
             hipLaunchKernelGGL(k_order_count, dim3(kOrderParts), dim3(256), 0, st, offs, n, bounds + kOrderBuckets);
             hipLaunchKernelGGL(k_order_scan_buckets, dim3(1), dim3(1024), 0, st, bounds, cursor);
-#ifdef STORMCK_PROBES  // probe knob STORMCK_ORDER_IDX=1: place the indices only, the sort gathers the offsets (A/B)
-            static const bool order_idx = [] {
-                const char* e = STORMCK_KNOB("STORMCK_ORDER_IDX");
-                return e && e[0] == '1';
-            }();
-            if (order_idx) {
-                hipLaunchKernelGGL(k_order_place<true>, dim3(kOrderPlaceParts), dim3(256), 0, st, offs, n, cursor, order,
-                                   s_offs);
-                hipLaunchKernelGGL(k_order_sort<true>, dim3(kOrderBuckets), dim3(256), 0, st, lens, bounds, order, s_offs,
-                                   s_lens, offs);
-            } else
-#endif
-            {
-                hipLaunchKernelGGL(k_order_place<false>, dim3(kOrderPlaceParts), dim3(256), 0, st, offs, n, cursor, order,
-                                   s_offs);
-                hipLaunchKernelGGL(k_order_sort<false>, dim3(kOrderBuckets), dim3(256), 0, st, lens, bounds, order, s_offs,
-                                   s_lens, offs);
-            }
+            with_consts([&](auto IDX) {
+                if constexpr (kProbes || !STORMCK_V(IDX)) {
+                    hipLaunchKernelGGL(k_order_place<STORMCK_V(IDX)>, dim3(kOrderPlaceParts), dim3(256), 0, st, offs, n,
+                                       cursor, order, s_offs);
+                    hipLaunchKernelGGL(k_order_sort<STORMCK_V(IDX)>, dim3(kOrderBuckets), dim3(256), 0, st, lens, bounds,
+                                       order, s_offs, s_lens, offs);
+                }
+            }, p.idx);
 #ifdef STORMCK_PROBES
-            // rejected (round 4): each group's rows re-dealt by length rank, rotated per
-            // workgroup step (kernels.h k_order_rank): 0.794 against 0.848 of 8 TB/s
-            if (lens && persistent && rank_on() && n / kGldsBlocks > 0)
+            if (p.rank)
                 hipLaunchKernelGGL(k_order_rank, dim3(static_cast<unsigned>(n / kGldsBlocks)), dim3(kGldsBlocks), 0, st,
                                    order, s_offs, s_lens, static_cast<uint64_t>(grid.x));
 #endif
             lens = s_lens;
             offs = s_offs;
-#define STORMCK_ORD(SK, LN)                                                                                      \
-    hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, false, kGldsWaves, SK, LN, true, true>), grid,       \
-                       dim3(kGldsThreads), 0, st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad, order)
-#ifdef STORMCK_PROBES  // probe knob STORMCK_GATHER_CONTIG=1: contiguous group runs per workgroup
-#define STORMCK_ORDC(LN)                                                                                         \
-    hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, false, kGldsWaves, kSkewTiles, LN, true, true, true>), \
-                       grid, dim3(kGldsThreads), 0, st, base, stride, lens, len, offs, n, out, expected, first_bad,    \
-                       n_bad, order)
-            static const bool contig = [] {
-                const char* e = STORMCK_KNOB("STORMCK_GATHER_CONTIG");
-                return e && e[0] == '1';
-            }();
-            if (persistent && contig) {
-                if (lens) STORMCK_ORDC(true);
-                else STORMCK_ORDC(false);
-            } else
-#undef STORMCK_ORDC
-#endif
-            if (defer) {
-#define STORMCK_ORDS(SK, LN)                                                                                     \
-    hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, false, kGldsWaves, SK, LN, true>), grid,            \
-                       dim3(kGldsThreads), 0, st, base, stride, lens, len, offs, n, s_out, expected, first_bad, n_bad, \
-                       nullptr)
-                if (persistent) {
-                    if (lens) STORMCK_ORDS(kSkewTiles, true);
-                    else STORMCK_ORDS(kSkewTiles, false);
+            const bool scatter = p.defer && !p.contig;  // hashed into the sorted positions, scattered after
+            with_consts([&](auto SKEW, auto LENS, auto CONTIG, auto DEFER) {
+                constexpr int skew = STORMCK_V(SKEW) ? kSkewTiles : 0;
+                if constexpr (STORMCK_V(CONTIG)) {
+                    if constexpr (kProbes && STORMCK_V(SKEW))
+                        hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, false, kGldsWaves, kSkewTiles,
+                                                             STORMCK_V(LENS), true, true, true>),
+                                           grid, block, 0, st, base, stride, lens, len, offs, n, out, expected, first_bad,
+                                           n_bad, order);
+                } else if constexpr (STORMCK_V(DEFER)) {
+                    hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, false, kGldsWaves, skew, STORMCK_V(LENS), true>),
+                                       grid, block, 0, st, base, stride, lens, len, offs, n, s_out, expected, first_bad, n_bad,
+                                       nullptr);
                 } else {
-                    if (lens) STORMCK_ORDS(0, true);
-                    else STORMCK_ORDS(0, false);
+                    hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, false, kGldsWaves, skew, STORMCK_V(LENS), true,
+                                                         true>),
+                                       grid, block, 0, st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad,
+                                       order);
                 }
-#undef STORMCK_ORDS
-                hipLaunchKernelGGL(k_order_scatter, dim3(2048), dim3(256), 0, st, order, s_out, out, n);
-            } else if (persistent) {
-                if (lens) STORMCK_ORD(kSkewTiles, true);
-                else STORMCK_ORD(kSkewTiles, false);
-            } else {
-                if (lens) STORMCK_ORD(0, true);
-                else STORMCK_ORD(0, false);
-            }
-#undef STORMCK_ORD
+            }, p.persistent, q.lens, p.contig, scatter);
+            if (scatter) hipLaunchKernelGGL(k_order_scatter, dim3(2048), dim3(256), 0, st, order, s_out, out, n);
             HIP_TRY(hipGetLastError());
             HIP_TRY(hipFreeAsync(ws, st));
             return STORMCK_OK;
         }
-#define STORMCK_VAR(VER, W, SK, LN, OF)                                                                          \
-    hipLaunchKernelGGL((k_xxh64_glds_var<kTileStripes, kAuxNT, VER, W, SK, LN, OF>), grid, dim3(64 * W), 0, st, base, \
-                       stride, lens, len, offs, n, out, expected, first_bad, n_bad, nullptr)
-#ifdef STORMCK_PROBES  // the 2-wave workgroups before round 3
-#define STORMCK_VAR_PROBES(LN, OF)                                                                               \
-        if (!big && vw == 2) {                                                                                   \
-            if (verify) STORMCK_VAR(true, 2, 0, LN, OF);                                                         \
-            else STORMCK_VAR(false, 2, 0, LN, OF);                                                               \
-        } else
-#else
-#define STORMCK_VAR_PROBES(LN, OF)
-#endif
-#define STORMCK_VAR_SHAPE(LN, OF)                                                                                \
-    do {                                                                                                         \
-        STORMCK_VAR_PROBES(LN, OF)                                                                               \
-        if (!big && vw == 1) {                                                                                   \
-            if (verify) STORMCK_VAR(true, 1, 0, LN, OF);                                                         \
-            else STORMCK_VAR(false, 1, 0, LN, OF);                                                               \
-        } else if (!big) {                                                                                       \
-            if (verify) STORMCK_VAR(true, 3, 0, LN, OF);                                                         \
-            else STORMCK_VAR(false, 3, 0, LN, OF);                                                               \
-        } else if (persistent) {                                                                                 \
-            if (verify) STORMCK_VAR(true, kGldsWaves, kSkewTiles, LN, OF);                                       \
-            else STORMCK_VAR(false, kGldsWaves, kSkewTiles, LN, OF);                                             \
-        } else {                                                                                                 \
-            if (verify) STORMCK_VAR(true, kGldsWaves, 0, LN, OF);                                                \
-            else STORMCK_VAR(false, kGldsWaves, 0, LN, OF);                                                      \
-        }                                                                                                        \
-    } while (0)
-        if (lens && offs) STORMCK_VAR_SHAPE(true, true);
-        else if (lens) STORMCK_VAR_SHAPE(true, false);
-        else STORMCK_VAR_SHAPE(false, true);
-#undef STORMCK_VAR_SHAPE
-#undef STORMCK_VAR_PROBES
-#undef STORMCK_VAR
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
+        case Kernel::Glds:  // the 8-wave workgroups synchronise their ring; 4 waves: probe build
+            with_int<1, 2, 3, 4, kGldsWaves>(p.waves, [&](auto W) {
+                with_consts([&](auto VER) {
+                    constexpr int w = STORMCK_V(W);
+                    if constexpr (kProbes || w != 4)
+                        hipLaunchKernelGGL((k_xxh64_glds<kTileStripes, kRing, kAuxNT, true, STORMCK_V(VER), w, w == kGldsWaves>),
+                                           grid, block, 0, st, base, stride, len, n, out, expected, first_bad, n_bad);
+                }, q.verify);
+            });
+            break;
+        case Kernel::GldsSkew:
+            with_consts([&](auto VER) {
+                hipLaunchKernelGGL((k_xxh64_glds_skew<kTileStripes, kAuxNT, STORMCK_V(VER), kGldsWaves, kSkewTiles>), grid,
+                                   block, 0, st, base, stride, len, n, out, expected, first_bad, n_bad);
+            }, q.verify);
+            break;
+        case Kernel::QuadSpread:
+            with_consts([&](auto LENS, auto OFFS, auto VER) {
+                hipLaunchKernelGGL((k_xxh64_quad<kU, STORMCK_V(LENS), STORMCK_V(OFFS), STORMCK_V(VER), false, kQuadSpreadDepth, 64>),
+                                   grid, block, 0, st, base, stride, lens, len, offs, n, out, expected, first_bad, n_bad);
+            }, q.lens, q.offs, q.verify);
+            break;
+        default:  // Kernel::Quad
+            with_consts([&](auto LENS, auto OFFS, auto VER) {
+                hipLaunchKernelGGL((k_xxh64_quad<kU, STORMCK_V(LENS), STORMCK_V(OFFS), STORMCK_V(VER)>), grid, block, 0, st,
+                                   base, stride, lens, len, offs, n, out, expected, first_bad, n_bad);
+            }, q.lens, q.offs, q.verify);
     }
-    // Uniform batches from 36 blocks per CU up to kBigBatch: the LDS-DMA kernel in
-    // W-wave workgroups (16*W blocks each), W in {1, 3} chosen to minimise the blocks of
-    // the busiest CU, ceil(workgroups / CUs) * 16W (ties: 3). us per launch of 31,808 B
-    // blocks, against the 256-thread quad / 2-wave LDS-DMA kernels before (rocprof-free
-    // HIP events, profiles/r03_mid/w*): 10,000 54.2 (60.9), 10,240 54.6 (60.1), 12,288
-    // 60.3 (65.6), 16,384 77.7 (81.8), 20,000 101.7 (112.2), 24,575 122.1 (126.3). Below
-    // it the quad kernels win (8,192 / 8,704: 39.9 / 47.9 against 51.6 / 52.2 for 3 waves;
-    // 9,216 / 9,728: 54.0 / 58.7 against 53.0 / 53.8, profiles/r03_mid/unilo*). Probe knob
-    // STORMCK_MID_WAVES = 1-4 forces W for every batch above one wave per CU; 5 = the
-    // kernels before.
-    static const int mid_knob = [] {
-        const char* e = STORMCK_KNOB("STORMCK_MID_WAVES");
-        return e ? std::atoi(e) : 0;
-    }();
-    // From kBigBatch up to kBigW blocks: 3-wave workgroups instead of the big path's
-    // 8-wave ones when that puts at most 3/4 of the blocks on the busiest CU (a batch a
-    // little above a multiple of 128 blocks per CU would leave most CUs with one 8-wave
-    // workgroup and some with two). 36,864 / 40,000 blocks: 179.8 / ~222 us against
-    // 237.3 / 240.7; 1-wave workgroups lost there (24,641: 132 against 119.6 us; 57,344:
-    // 291 against 264), profiles/r03_mid/bigw*.
-    int mid_waves = 0;
-    const uint64_t ncu_m = cu_count();
-    auto busiest = [&](uint64_t w) { return (((n + 16 * w - 1) / (16 * w)) + ncu_m - 1) / ncu_m * 16 * w; };
-    if (ncu_m > 0 && n < kBigBatch) {
-        if (mid_knob >= 1 && mid_knob <= 4) {
-            if (n > 16 * ncu_m) mid_waves = mid_knob;
-        } else if (mid_knob == 0 && n >= 36 * ncu_m) {
-            mid_waves = busiest(1) < busiest(3) ? 1 : 3;
-        }
-    } else if (ncu_m > 0 && n < kBigW && mid_knob == 0 && big_w_on()) {
-        if (4 * busiest(3) <= 3 * busiest(8)) mid_waves = 3;
-    }
-    if (mid_waves > 0 && !lens && !offs && (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (stride & 15) == 0 &&
-        len >= 32u * kTileStripes) {
-        const dim3 g(static_cast<unsigned>((n + 16 * mid_waves - 1) / (16 * mid_waves)));
-#define STORMCK_MIDW(W, VER)                                                                                      \
-    hipLaunchKernelGGL((k_xxh64_glds<kTileStripes, kRing, kAuxNT, true, VER, W, false>), g, dim3(64 * W), 0, st, base, \
-                       stride, len, n, out, expected, first_bad, n_bad)
-        if (mid_waves == 1) {
-            if (verify) STORMCK_MIDW(1, true);
-            else STORMCK_MIDW(1, false);
-        } else if (mid_waves == 2) {
-            if (verify) STORMCK_MIDW(2, true);
-            else STORMCK_MIDW(2, false);
-#ifdef STORMCK_PROBES
-        } else if (mid_waves == 4) {
-            if (verify) STORMCK_MIDW(4, true);
-            else STORMCK_MIDW(4, false);
-#endif
-        } else {
-            if (verify) STORMCK_MIDW(3, true);
-            else STORMCK_MIDW(3, false);
-        }
-#undef STORMCK_MIDW
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
-    }
-    if (n >= kMidBatch && !lens && !offs && (reinterpret_cast<uintptr_t>(base) & 15) == 0 && (stride & 15) == 0 &&
-        len >= 32u * kTileStripes) {
-        if (n < kBigBatch) {
-            const dim3 grid(static_cast<unsigned>((n + 16 * kMidWaves - 1) / (16 * kMidWaves)));
-            if (verify)
-                hipLaunchKernelGGL((k_xxh64_glds<kTileStripes, kRing, kAuxNT, true, true, kMidWaves, false>), grid,
-                                   dim3(64 * kMidWaves), 0, st, base, stride, len, n, out, expected, first_bad, n_bad);
-            else
-                hipLaunchKernelGGL((k_xxh64_glds<kTileStripes, kRing, kAuxNT, true, false, kMidWaves, false>), grid,
-                                   dim3(64 * kMidWaves), 0, st, base, stride, len, n, out, expected, first_bad, n_bad);
-            HIP_TRY(hipGetLastError());
-            return STORMCK_OK;
-        }
-        const uint64_t wgs = (n + kGldsBlocks - 1) / kGldsBlocks;
-        if (wgs > 0x7fffffffULL) return fail(STORMCK_EINVAL, "batch too large for one launch");
-        const uint64_t cus = cu_count();
-        const uint64_t steps_per_wg = (wgs + cus - 1) / cus * ((len / 32) / kTileStripes);
-        // probe knob STORMCK_SKEW_MIN_STEPS: the skewed kernel's threshold (A/B of the two
-        // kernels at the c3 arena's 2M-block launches)
-        static const uint64_t skew_min = [] {
-            const char* e = STORMCK_KNOB("STORMCK_SKEW_MIN_STEPS");
-            return e ? std::strtoull(e, nullptr, 10) : kSkewMinSteps;
-        }();
-        if (cus > 0 && wgs >= cus && steps_per_wg >= skew_min) {
-            // large batch: persistent workgroups, one per CU, waves' streams 4 KiB apart
-#define STORMCK_SKEW(VER)                                                                                        \
-    hipLaunchKernelGGL((k_xxh64_glds_skew<kTileStripes, kAuxNT, VER, kGldsWaves, kSkewTiles>),                 \
-                       dim3(static_cast<unsigned>(cus)), dim3(kGldsThreads), 0, st, base, stride, len, n, out,  \
-                       expected, first_bad, n_bad)
-            if (verify) STORMCK_SKEW(true);
-            else STORMCK_SKEW(false);
-#undef STORMCK_SKEW
-            HIP_TRY(hipGetLastError());
-            return STORMCK_OK;
-        }
-        if (verify)
-            hipLaunchKernelGGL((k_xxh64_glds<kTileStripes, kRing, kAuxNT, true, true, kGldsWaves>),
-                               dim3(static_cast<unsigned>(wgs)), dim3(kGldsThreads), 0, st, base, stride, len, n, out,
-                               expected, first_bad, n_bad);
-        else
-            hipLaunchKernelGGL((k_xxh64_glds<kTileStripes, kRing, kAuxNT, true, false, kGldsWaves>),
-                               dim3(static_cast<unsigned>(wgs)), dim3(kGldsThreads), 0, st, base, stride, len, n, out,
-                               expected, first_bad, n_bad);
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
-    }
-    // General path (per-block lengths / explicit offsets / any alignment): register quad
-    // kernel. A batch of at most one wave per CU (16 blocks a wave) runs in one-wave
-    // workgroups, so every wave has a CU of its own, with four groups of loads in flight:
-    // the quad kernel's 16 scattered 32-byte pieces per load instruction make a CU's
-    // address path the limit, 2 waves on a CU cost as much as 4 (profiles/r03_quad/:
-    // 2,049 / 3,072 / 4,096 blocks of 31,808 B in 25.2 / 27.9 / 31.8 us against 34.6 /
-    // 35.0 / 35.1 in 256-thread workgroups). Past one wave per CU it loses (6,144 /
-    // 8,192 blocks: 38.5 / 48.8 us against 35.8 / 39.7 in 256-thread workgroups,
-    // profiles/r03_mid/spread_*.txt), and so does a one-wave LDS-DMA ring of 4-9 tile
-    // slots (38-60 us over 2,064-8,192 blocks, profiles/r03_mid/probe_*). Probe knob
-    // STORMCK_QUAD_SPREAD = waves per CU it covers (0 disables).
-    static const uint64_t spread_mult = [] {  // batches of up to spread_mult waves per CU
-        const char* e = STORMCK_KNOB("STORMCK_QUAD_SPREAD");
-        return e ? static_cast<uint64_t>(std::atoi(e)) : uint64_t{1};
-    }();
-    const uint64_t ncu_q = cu_count();
-    if (ncu_q > 0 && n <= 16 * spread_mult * ncu_q) {
-        const dim3 g(static_cast<unsigned>((n + 15) / 16));
-#define STORMCK_SPREAD(LENS, OFFS, VER)                                                                               \
-    hipLaunchKernelGGL((k_xxh64_quad<kU, LENS, OFFS, VER, false, kQuadSpreadDepth, 64>), g, dim3(64), 0, st, base, stride, \
-                       lens, len, offs, n, out, expected, first_bad, n_bad)
-        if (!verify) {
-            if (lens && offs) STORMCK_SPREAD(true, true, false);
-            else if (lens) STORMCK_SPREAD(true, false, false);
-            else if (offs) STORMCK_SPREAD(false, true, false);
-            else STORMCK_SPREAD(false, false, false);
-        } else {
-            if (lens && offs) STORMCK_SPREAD(true, true, true);
-            else if (lens) STORMCK_SPREAD(true, false, true);
-            else if (offs) STORMCK_SPREAD(false, true, true);
-            else STORMCK_SPREAD(false, false, true);
-        }
-#undef STORMCK_SPREAD
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
-    }
-    dim3 grid;
-    if (!grid_for(n * 4, &grid)) return fail(STORMCK_EINVAL, "batch too large for one launch");
-#define STORMCK_LAUNCH(LENS, OFFS, VER)                                                                         \
-    hipLaunchKernelGGL((k_xxh64_quad<kU, LENS, OFFS, VER>), grid, dim3(kThreads), 0, st, base, stride, lens, len, \
-                       offs, n, out, expected, first_bad, n_bad)
-    if (!verify) {
-        if (lens && offs) STORMCK_LAUNCH(true, true, false);
-        else if (lens) STORMCK_LAUNCH(true, false, false);
-        else if (offs) STORMCK_LAUNCH(false, true, false);
-        else STORMCK_LAUNCH(false, false, false);
-    } else {
-        if (lens && offs) STORMCK_LAUNCH(true, true, true);
-        else if (lens) STORMCK_LAUNCH(true, false, true);
-        else if (offs) STORMCK_LAUNCH(false, true, true);
-        else STORMCK_LAUNCH(false, false, true);
-    }
-#undef STORMCK_LAUNCH
     HIP_TRY(hipGetLastError());
     return STORMCK_OK;
 }
@@ -1692,11 +1286,7 @@ int stormck_checksum(const void* p, uint64_t n_bytes, uint64_t* out) {
     // 256 MiB (DESIGN_LOG.md §5, "Single calls"). The crossover is therefore "never";
     // STORMCK_SINGLE_GPU_MIN=<bytes> sends single calls of at least that many bytes to
     // the device (A/B measurement only).
-    static const uint64_t gpu_min = [] {
-        const char* e = STORMCK_KNOB("STORMCK_SINGLE_GPU_MIN");
-        return e ? std::strtoull(e, nullptr, 10) : UINT64_MAX;
-    }();
-    if (n_bytes >= gpu_min) return stormck_checksum_gpu(p, n_bytes, out);
+    if (n_bytes >= knobs().single_gpu_min) return stormck_checksum_gpu(p, n_bytes, out);
     *out = stormck_xxh64(p, n_bytes);
     return STORMCK_OK;
 }
@@ -1774,70 +1364,34 @@ int stormck_pointer_level_device(const uint64_t* d_child_cs, uint64_t m, uint64_
     if (fanout == 0 || fanout > kMaxFanout) return fail(STORMCK_EINVAL, "fanout out of range");
     int rc = device_check();
     if (rc) return rc;
-    const uint64_t pm = (m + fanout - 1) / fanout;
-    if (pm <= kWideNodes && pointer_block_size(fanout) <= kNodeLds) {
-        // a few nodes: one workgroup each, words synthesised into LDS by all its threads
-        hipLaunchKernelGGL(k_pointer_level_wide, dim3(static_cast<unsigned>(pm)), dim3(kThreads), 0,
-                           static_cast<hipStream_t>(stream), d_child_cs, m, child_addr_base, rev, child_type, fanout,
-                           d_parent_cs);
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
+    const Plan p = plan_pointer_level((m + fanout - 1) / fanout, fanout, cu_count(), knobs());
+    const dim3 grid(p.grid), block(p.block);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    switch (p.kernel) {
+        case Kernel::TooLarge:
+            return fail(STORMCK_EINVAL, "level too large");
+        case Kernel::Wide:
+            hipLaunchKernelGGL(k_pointer_level_wide, grid, block, 0, st, d_child_cs, m, child_addr_base, rev, child_type,
+                               fanout, d_parent_cs);
+            break;
+        case Kernel::PointerPc:  // 2 or 4 chain waves per workgroup: probe build (rejected)
+            with_int<1, 2, 4>(p.waves, [&](auto C) {
+                with_consts([&](auto SR) {
+                    if constexpr (STORMCK_V(C) == 1 ? !STORMCK_V(SR) : kProbes)
+                        hipLaunchKernelGGL((k_pointer_level_pc<STORMCK_POINTERS_PER_BLOCK, kRingTile, kRingPrefetch, STORMCK_V(C),
+                                                               STORMCK_V(SR)>),
+                                           grid, block, 0, st, d_child_cs, m, child_addr_base, rev, child_type, d_parent_cs);
+                }, p.simd_roles);
+            });
+            break;
+        default:  // Kernel::Quad
+            hipLaunchKernelGGL(k_pointer_level, grid, block, 0, st, d_child_cs, m, child_addr_base, rev, child_type, fanout,
+                               d_parent_cs);
     }
-    // probe knob STORMCK_POINTER_RING: "0" = the register-quad kernel; default: the
-    // producer / chain wave pair (k_pointer_level_pc). Measured alternatives (one wave
-    // producing and hashing, 30- and 45-stripe tiles, prefetch 4 and 12 tiles, two pairs
-    // per workgroup, one producer for two chain waves): DESIGN_LOG.md §5, profiles/r02_merkle/.
-    static const int ring_mode = [] {
-        const char* e = STORMCK_KNOB("STORMCK_POINTER_RING");
-        return e ? std::atoi(e) : 2;
-    }();
-    if (ring_mode != 0 && fanout == STORMCK_POINTERS_PER_BLOCK) {
-        // storm's fan-out: 16 nodes per workgroup, premultiplied words staged in LDS
-        // C chain waves per workgroup (and C producers). C = 1: the dispatcher already
-        // puts the chain waves of 2-wave workgroups on distinct SIMDs at every level size
-        // (tools/hwid_probe.hip), and one workgroup per CU with C = 2 / 4 (chains on
-        // distinct SIMDs by pc_role) measured slower: 35.2 / 41.0 us against 31.7 / 37.9
-        // for the 6,991- / 13,982-node levels (profiles/r03_merkle_simd/). Probe knobs:
-        // STORMCK_POINTER_C = 2 / 4 (or 0: the fewest C that keeps one workgroup per CU),
-        // STORMCK_POINTER_SIMD=0 takes roles by wave index.
-        constexpr uint32_t F = STORMCK_POINTERS_PER_BLOCK;
-        static const int fixed_c = [] {
-            const char* e = STORMCK_KNOB("STORMCK_POINTER_C");
-            return e ? std::atoi(e) : 1;
-        }();
-        static const bool simd_roles = [] {
-            const char* e = STORMCK_KNOB("STORMCK_POINTER_SIMD");
-            return !(e && e[0] == '0');
-        }();
-        const uint64_t chains = (pm + 15) / 16, ncu = cu_count() ? cu_count() : 256;
-        const int c = fixed_c == 1 || fixed_c == 2 || fixed_c == 4 ? fixed_c
-                      : chains <= ncu ? 1 : chains <= 2 * ncu ? 2 : 4;
-        const uint64_t groups = (chains + c - 1) / c;
-        if (groups > 0x7fffffffULL) return fail(STORMCK_EINVAL, "level too large");
-        const dim3 grid(static_cast<unsigned>(groups));
-        hipStream_t st = static_cast<hipStream_t>(stream);
-#define STORMCK_PC(C, SR)                                                                                       \
-    hipLaunchKernelGGL((k_pointer_level_pc<F, kRingTile, kRingPrefetch, C, SR>), grid, dim3(128 * C), 0, st, \
-                       d_child_cs, m, child_addr_base, rev, child_type, d_parent_cs)
-#ifdef STORMCK_PROBES  // 2 or 4 chain waves per workgroup (rejected)
-        if (c == 2) { if (simd_roles) STORMCK_PC(2, true); else STORMCK_PC(2, false); }
-        else if (c == 4) { if (simd_roles) STORMCK_PC(4, true); else STORMCK_PC(4, false); }
-        else
-#else
-        (void)simd_roles;
-#endif
-        STORMCK_PC(1, false);  // one chain wave: its producer cannot take its SIMD
-#undef STORMCK_PC
-        HIP_TRY(hipGetLastError());
-        return STORMCK_OK;
-    }
-    dim3 grid;
-    if (!grid_for(pm * 4, &grid)) return fail(STORMCK_EINVAL, "level too large");
-    hipLaunchKernelGGL(k_pointer_level, grid, dim3(kThreads), 0, static_cast<hipStream_t>(stream), d_child_cs, m,
-                       child_addr_base, rev, child_type, fanout, d_parent_cs);
     HIP_TRY(hipGetLastError());
     return STORMCK_OK;
 }
+
 
 int stormck_pointer_node_device(const stormck_pointer* d_entries, const uint8_t* d_types, uint32_t count,
                                 uint32_t fanout, uint64_t* d_out_cs, void* stream) {
@@ -2100,84 +1654,40 @@ int stormck_key_tags_device(const void* d_keys, uint64_t stride, const uint64_t*
     if (!d_keys || !d_out) return fail(STORMCK_EINVAL, "null device pointer");
     int rc = device_check();
     if (rc) return rc;
-    dim3 grid;
-    if (!grid_for(n, &grid)) return fail(STORMCK_EINVAL, "batch too large for one launch");
-    hipStream_t st = static_cast<hipStream_t>(stream);
     const uint8_t* k = static_cast<const uint8_t*>(d_keys);
-    if (!d_offsets && !d_lens && stride >= 16 && stride <= 256 && (stride & 15) == 0 && len <= stride &&
-        (reinterpret_cast<uintptr_t>(k) & 15) == 0 && n >= 64) {
-        // whole batches of 64 keys through a per-wave LDS-DMA prefetch ring: keys up to
-        // 64 bytes (storm's 48-byte keys) take the 4-slot ring with a compile-time
-        // stride (and a compile-time length when keys fill their stride), longer ones the
-        // runtime-stride double buffer
-        const uint64_t batches = n / 64;
-        constexpr uint32_t kPerWave = 8;
-        constexpr int kKeyRing = 4;
+    const KeyTagsPlan p = plan_key_tags(stride, len, n, d_offsets != nullptr, d_lens != nullptr,
+                                        static_cast<unsigned>(reinterpret_cast<uintptr_t>(k) & 15));
+    if (p.too_large) return fail(STORMCK_EINVAL, "batch too large for one launch");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (p.batches > 0) {
         // tags leave by non-temporal stores: the 8 B-per-key write stream costs the
         // read stream about a quarter of the rate, nt stores recover ~3 %
         // (tools/probe_keys.hip, profiles/r02_keys/)
         constexpr int kKeyStore = 1;
-        const uint64_t waves = (batches + kPerWave - 1) / kPerWave;
-        const uint64_t wgs = (waves + 3) / 4;
-        if (wgs > 0x7fffffffULL) return fail(STORMCK_EINVAL, "batch too large for one launch");
-        const dim3 grid_k(static_cast<unsigned>(wgs));
-        const size_t ring_lds = 4 * kKeyRing * 64 * static_cast<size_t>(stride);
-        switch (stride) {
-            case 16:
-                if (len == 16)
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 1, kKeyRing, kPerWave, 16, kKeyStore>), grid_k, dim3(kThreads), ring_lds,
-                                       st, k, len, batches, d_out);
-                else
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 1, kKeyRing, kPerWave, 0, kKeyStore>), grid_k, dim3(kThreads), ring_lds, st,
-                                       k, len, batches, d_out);
-                break;
-            case 32:
-                if (len == 32)
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 2, kKeyRing, kPerWave, 32, kKeyStore>), grid_k, dim3(kThreads), ring_lds,
-                                       st, k, len, batches, d_out);
-                else
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 2, kKeyRing, kPerWave, 0, kKeyStore>), grid_k, dim3(kThreads), ring_lds, st,
-                                       k, len, batches, d_out);
-                break;
-            case 48:
-                if (len == 48)
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 3, kKeyRing, kPerWave, 48, kKeyStore>), grid_k, dim3(kThreads), ring_lds,
-                                       st, k, len, batches, d_out);
-                else
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 3, kKeyRing, kPerWave, 0, kKeyStore>), grid_k, dim3(kThreads), ring_lds, st,
-                                       k, len, batches, d_out);
-                break;
-            case 64:
-                if (len == 64)
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 4, kKeyRing, kPerWave, 64, kKeyStore>), grid_k, dim3(kThreads), ring_lds,
-                                       st, k, len, batches, d_out);
-                else
-                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, 4, kKeyRing, kPerWave, 0, kKeyStore>), grid_k, dim3(kThreads), ring_lds, st,
-                                       k, len, batches, d_out);
-                break;
-            default:
-                hipLaunchKernelGGL(k_key_tags_lds<kAuxNT>, grid_k, dim3(kThreads), 4 * 2 * 64 * static_cast<size_t>(stride),
-                                   st, k, static_cast<uint32_t>(stride), len, batches, kPerWave, d_out);
-        }
+        if (p.pieces <= 4)
+            with_int<1, 2, 3, 4>(p.pieces, [&](auto P) {
+                with_consts([&](auto FIXED) {
+                    hipLaunchKernelGGL((k_key_tags_ring<kAuxNT, STORMCK_V(P), kKeyRing, kKeysPerWave,
+                                                        STORMCK_V(FIXED) ? 16 * STORMCK_V(P) : 0, kKeyStore>),
+                                       dim3(p.grid), dim3(kThreads), p.lds, st, k, len, p.batches, d_out);
+                }, p.fixed_len);
+            });
+        else
+            hipLaunchKernelGGL(k_key_tags_lds<kAuxNT>, dim3(p.grid), dim3(kThreads), p.lds, st, k,
+                               static_cast<uint32_t>(stride), len, p.batches, kKeysPerWave, d_out);
         HIP_TRY(hipGetLastError());
-        const uint64_t done = batches * 64;
-        if (done == n) return STORMCK_OK;
-        k += done * stride;
-        d_out += done;
-        n -= done;
-        if (!grid_for(n, &grid)) return fail(STORMCK_EINVAL, "batch too large for one launch");
+        if (p.tail == 0) return STORMCK_OK;
+        k += p.batches * 64 * stride;
+        d_out += p.batches * 64;
     }
-    if (d_offsets && d_lens)
-        hipLaunchKernelGGL((k_key_tags<true, true>), grid, dim3(kThreads), 0, st, k, stride, d_offsets, d_lens, len, n, d_out);
-    else if (d_offsets)
-        hipLaunchKernelGGL((k_key_tags<true, false>), grid, dim3(kThreads), 0, st, k, stride, d_offsets, d_lens, len, n, d_out);
-    else if (d_lens)
-        hipLaunchKernelGGL((k_key_tags<false, true>), grid, dim3(kThreads), 0, st, k, stride, d_offsets, d_lens, len, n, d_out);
-    else
-        hipLaunchKernelGGL((k_key_tags<false, false>), grid, dim3(kThreads), 0, st, k, stride, d_offsets, d_lens, len, n, d_out);
+    with_consts([&](auto OFFS, auto LENS) {
+        hipLaunchKernelGGL((k_key_tags<STORMCK_V(OFFS), STORMCK_V(LENS)>), dim3(p.tail_grid), dim3(kThreads), 0, st, k, stride,
+                           d_offsets, d_lens, len, p.tail, d_out);
+    }, d_offsets != nullptr, d_lens != nullptr);
     HIP_TRY(hipGetLastError());
     return STORMCK_OK;
 }
+
 
 int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
                           uint64_t* last_allocated_block, uint64_t* out_checksums, void* stream) {
@@ -2264,7 +1774,7 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
     const bool prefix0 = nu == 0 || upper_min.load() == n0;
     // the LDS-DMA level kernels need 16-byte aligned rows, and pay only when blocks are
     // longer than a few of their 512-byte rows (as launch_checksum's kVarMinLen)
-    const bool glds_levels = !misaligned.load() && longest.load() > var_min_len();
+    const bool glds_levels = !misaligned.load() && longest.load() > knobs().var_min_len;
     pt.mark("heights");
 
     // device resources before the records are touched: a failure here leaves them as given
@@ -2319,72 +1829,35 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
     auto idx_at = [&](uint64_t k) -> uint64_t { return order.empty() ? k : order[k]; };
 
     hipStream_t st = static_cast<hipStream_t>(stream);
-    uint64_t commit_wide = kCommitWide;
-    if (const char* e = STORMCK_KNOB("STORMCK_COMMIT_WIDE")) commit_wide = std::strtoull(e, nullptr, 10);  // probe knob
-    static const bool commit_multi = [] {
-        const char* e = STORMCK_KNOB("STORMCK_COMMIT_MULTI");  // probe knob: "0" disables
-        return !(e && e[0] == '0');
-    }();
+    const Knobs kn = commit_knobs();
     const uint64_t ncu = cu_count();
-    static const bool commit_midw = [] {  // probe knob STORMCK_COMMIT_MIDW=0: the launches before (A/B)
-        const char* e = STORMCK_KNOB("STORMCK_COMMIT_MIDW");
-        return !(e && e[0] == '0');
-    }();
+    uint8_t* arena = static_cast<uint8_t*>(d_arena);
     auto launch_level = [&](uint64_t lo, uint64_t cnt) -> int {
-        auto busiest = [&](uint64_t w) { return (((cnt + 16 * w - 1) / (16 * w)) + ncu - 1) / ncu * 16 * w; };
-        if (commit_midw && glds_levels && ncu > 0 && cnt >= 39 * ncu &&
-            (cnt < kBigBatch || (cnt < kBigW && big_w_on() && 4 * busiest(3) <= 3 * busiest(8)))) {
-            // mid-size levels: the LDS-DMA ring in 3- or 1-wave workgroups, whichever puts
-            // fewer blocks on the busiest CU; from kBigBatch, 3-wave ones where they cut the
-            // busiest CU's blocks by a quarter (as launch_checksum's uniform path)
-            if (cnt < kBigBatch && busiest(1) < busiest(3))
-                hipLaunchKernelGGL((k_commit_level_glds<kTileStripes, kAuxNT, 1>), dim3(static_cast<unsigned>((cnt + 15) / 16)),
-                                   dim3(64), 0, st, static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs);
-            else
-                hipLaunchKernelGGL((k_commit_level_glds<kTileStripes, kAuxNT, 3>), dim3(static_cast<unsigned>((cnt + 47) / 48)),
-                                   dim3(192), 0, st, static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs);
-        } else if (glds_levels && cnt >= kStreamBatch) {
-            // LDS-DMA ring, 8 waves x 128 blocks per workgroup (as the uniform fast path)
-            const uint64_t wgs = (cnt + kGldsBlocks - 1) / kGldsBlocks;
-            if (wgs > 0x7fffffffULL) return fail(STORMCK_EINVAL, "level too large");
-            hipLaunchKernelGGL((k_commit_level_glds<kTileStripes, kAuxNT, kGldsWaves>), dim3(static_cast<unsigned>(wgs)),
-                               dim3(kGldsThreads), 0, st, static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs);
-        } else if (cnt <= commit_wide) {
-            // one workgroup per block, premultiplied staging: the chain wave is alone on its SIMD
-            hipLaunchKernelGGL(k_commit_level_wide, dim3(static_cast<unsigned>(cnt)), dim3(kThreads), 0, st,
-                               static_cast<uint8_t*>(d_arena), d_blocks, lo, d_cs);
-        } else if (commit_multi && multi_bpw(cnt, ncu) > 0) {
-            // up to 5 (ring staging: 8) blocks per CU (a storm commit's leaves): wide-multi staging
-            const uint64_t bpw = multi_bpw(cnt, ncu);
-            const dim3 grid(static_cast<unsigned>((cnt + bpw - 1) / bpw));
-            const uint32_t ring_slots = pipe_staging();
-            uint32_t* fault = nullptr;  // the fault slot of the commit's stream
-            if (ring_slots) {
-                const int frc = fault_slot(st, &fault);
-                if (frc) return frc;
+        const Plan p = plan_commit_level(cnt, ncu, glds_levels, kn);
+        const dim3 grid(p.grid), block(p.block);
+        switch (p.kernel) {
+            case Kernel::TooLarge:
+                return fail(STORMCK_EINVAL, "level too large");
+            case Kernel::Glds:
+                with_int<1, 3, kGldsWaves>(p.waves, [&](auto W) {
+                    hipLaunchKernelGGL((k_commit_level_glds<kTileStripes, kAuxNT, STORMCK_V(W)>), grid, block, 0, st, arena,
+                                       d_blocks, lo, cnt, d_cs);
+                });
+                break;
+            case Kernel::Wide:
+                hipLaunchKernelGGL(k_commit_level_wide, grid, block, 0, st, arena, d_blocks, lo, d_cs);
+                break;
+            case Kernel::WideMulti: {
+                const int mrc = launch_wide_multi(p.multi, st, [&](auto BPW, auto RING, auto CHUNK, auto DBL, uint32_t* fault,
+                                                                   uint32_t stall) {
+                    hipLaunchKernelGGL((k_commit_level_multi<STORMCK_V(BPW), STORMCK_V(RING), STORMCK_V(CHUNK), STORMCK_V(DBL)>),
+                                       grid, block, 0, st, arena, d_blocks, lo, cnt, d_cs, fault, stall);
+                });
+                if (mrc) return mrc;
+                break;
             }
-            const uint32_t stall = debug_stall(st);
-#ifdef STORMCK_PROBES  // the rejected 16-block / whole-block-staging variants
-            if (ring_slots && bpw == kMultiBpwWide)
-                hipLaunchKernelGGL((k_commit_level_multi<kMultiBpwWide, kRingSlots, kChunkPiecesWide, true>), grid,
-                                   dim3(kThreads), 0, st, static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs,
-                                   fault, stall);
-            else if (!ring_slots)
-                hipLaunchKernelGGL((k_commit_level_multi<kMultiBpw, 0>), grid, dim3(kThreads), 0, st,
-                                   static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs, fault, stall);
-            else
-#endif
-            if (bpw == kMultiBpw)
-                hipLaunchKernelGGL((k_commit_level_multi<kMultiBpw, kRingSlots>), grid, dim3(kThreads), 0, st,
-                                   static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs, fault, stall);
-            else
-                hipLaunchKernelGGL((k_commit_level_multi<kMultiBpwRing, kRingSlots>), grid, dim3(kThreads), 0, st,
-                                   static_cast<uint8_t*>(d_arena), d_blocks, lo, cnt, d_cs, fault, stall);
-        } else {
-            dim3 grid;
-            if (!grid_for(cnt * 4, &grid)) return fail(STORMCK_EINVAL, "level too large");
-            hipLaunchKernelGGL(k_commit_level<kU>, grid, dim3(kThreads), 0, st, static_cast<uint8_t*>(d_arena), d_blocks,
-                               lo, cnt, d_cs);
+            default:  // Kernel::Quad
+                hipLaunchKernelGGL(k_commit_level<kU>, grid, block, 0, st, arena, d_blocks, lo, cnt, d_cs);
         }
         HIP_TRY(hipGetLastError());
         return STORMCK_OK;
@@ -2445,14 +1918,7 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
         // workgroup per CU) starts the device after a small upload; each next chunk is 3x
         // the previous, small enough that its records (56 B per block over PCIe) arrive
         // before the previous chunk's blocks (~32 KiB each at HBM rate) are hashed.
-        uint64_t next = 2 * kStreamBatch, growth = 3;
-        if (const char* e = STORMCK_KNOB("STORMCK_COMMIT_CHUNKS")) {  // tuning probe: "first,growth"
-            unsigned long long f = 0, gr = 0;
-            if (std::sscanf(e, "%llu,%llu", &f, &gr) == 2 && f >= 1 && gr >= 1) {
-                next = f;
-                growth = gr;
-            }
-        }
+        uint64_t next = kn.commit_first, growth = kn.commit_growth;
         // A small commit (storm's per-revision commit: ~1,200 leaves under one pointer
         // block) returns its checksums in one piece after the last level: an event
         // recorded between two launches holds the second one back by about 4 us

@@ -19,7 +19,7 @@ POINTERS_PER_BLOCK = 1200  # blocks/pointer/params.go:6
 # Batches the library may give to a ring-staged kernel (k_xxh64_wide_multi, whose
 # bounded waits report a stall in the stream's fault slot rather than in the output):
 # more than kWideBatch (128) blocks and at most kMultiBpwRing (8) per CU
-# (storm_amd/csrc/stormck.hip multi_bpw).
+# (storm_amd/csrc/dispatch.h multi_shape).
 _RING_MIN_EXCLUSIVE, _RING_PER_CU = 128, 8
 _cus = {}
 

@@ -1,5 +1,6 @@
 """Seeded random batches across the batch-size dispatch of launch_checksum
-(storm_amd/csrc/stormck.hip): one workgroup per block (<= 128), five staged blocks per
+(plan_checksum, storm_amd/csrc/dispatch.h; tests/test_dispatch_plan.py pins which kernel
+each size takes): one workgroup per block (<= 128), five staged blocks per
 workgroup (<= 5 per CU), 8 and 16 ring-staged blocks per workgroup (<= 16 per CU),
 register quad, LDS-staged streaming in 2- and 8-wave workgroups (uniform lengths:
 k_xxh64_glds; per-block lengths and gathered offsets: k_xxh64_glds_var); uniform lengths, per-block lengths and gathered offsets; 16-byte, 8-byte and

@@ -55,7 +55,7 @@ _lib.check(L.stormck_debug_partial_quad_selftest())
 res["selftest"] = count()
 rng = np.random.default_rng(5)
 bad = []
-# every batch class of launch_checksum: wide, wide-multi (5 / 8 per CU), quad spread,
+# every batch class of launch_checksum (plan_checksum, storm_amd/csrc/dispatch.h): wide, wide-multi (5 / 8 per CU), quad spread,
 # quad, LDS-DMA 1/3/8 waves and the persistent skewed form; uniform, per-block lengths,
 # gathered offsets, unaligned rows; checksum and verify
 for n, slot in [(1, 4096), (100, 4096), (1200, 32768), (2000, 32768), (3000, 8192), (8000, 4096), (9300, 32768),
