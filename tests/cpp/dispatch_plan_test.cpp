@@ -138,6 +138,35 @@ static void lengths_and_gathers() {
     gv.verify = true;
     expect("gather verify n=2^20", plan(gv), Kernel::GldsVar, 8192, 512, 8);
     expect("gather n=2^32", plan(gather(uint64_t{1} << 32)), Kernel::GldsVar, 256, 512, 8);
+    // offsets with one length for all blocks: the classes of the uniform batches up to 16 per CU,
+    // whatever the alignment (tests/test_dispatch_fuzz.py, tests/test_far_offsets_gpu.py)
+    expect("gather n=128", plan(gather(128)), Kernel::Wide, 128, 256);
+    expect_multi("gather n=1280", plan(gather(1280)), 5, 256);
+    expect_multi("gather n=1281", plan(gather(1281)), 8, 161);
+    expect("gather n=4096", plan(gather(4096)), Kernel::QuadSpread, 256, 64);
+    expect("gather n=4097", plan(gather(4097)), Kernel::Quad, 65, 256);
+    // 4,200-byte blocks are past kVarMinLen: the var kernel from 44 per CU, below it the quad
+    auto short_gather = [](uint64_t n, uint32_t len, bool lens) {
+        Query q = gather(n);
+        q.len = len;
+        q.lens = lens;
+        return q;
+    };
+    expect("gather n=11263 len=4200", plan(short_gather(11263, 4200, false)), Kernel::Quad, 176, 256);
+    expect("gather n=11264 len=4200", plan(short_gather(11264, 4200, false)), Kernel::GldsVar, 235, 192, 3);
+    expect("gather n=12289 len=4200", plan(short_gather(12289, 4200, false)), Kernel::GldsVar, 769, 64, 1);
+    expect("gather+lens n=11264 bound 4200", plan(short_gather(11264, 4200, true)), Kernel::GldsVar, 235, 192, 3);
+    expect("gather+lens n=12289 bound 4200", plan(short_gather(12289, 4200, true)), Kernel::GldsVar, 769, 64, 1);
+    expect("gather n=11264 len=4096", plan(short_gather(11264, 4096, false)), Kernel::Quad, 176, 256);
+    // strided rows 512 KiB apart, 4,099 bytes each
+    auto far_rows = [](uint64_t n) {
+        Query q = uniform(n, 4099);
+        q.stride = 524288;
+        return q;
+    };
+    expect("n=9215 stride 512K", plan(far_rows(9215)), Kernel::Quad, 144, 256);
+    expect("n=9216 stride 512K", plan(far_rows(9216)), Kernel::Glds, 192, 192, 3);
+    expect("lens n=11264 bound 4200", plan(with_lens(11264, 4200)), Kernel::GldsVar, 235, 192, 3);
 }
 
 static void commit_levels() {
@@ -155,6 +184,23 @@ static void commit_levels() {
     expect("commit 32768", level(32768), Kernel::Glds, 256, 512, 8);
     expect("commit 36864", level(36864), Kernel::Glds, 768, 192, 3);
     expect("commit 131072", level(131072), Kernel::Glds, 1024, 512, 8);
+    // kBigBatch itself: 512 three-wave workgroups -> 2 x 48 = 96 against 192 eight-wave ones -> 128: 3/4
+    expect("commit 24576", level(24576), Kernel::Glds, 512, 192, 3);
+    // the second level-0 chunk of a 140,000-leaf commit: 2,234 -> 9 x 48 = 432 against 838 -> 4 x 128 = 512
+    expect("commit 107232", level(107232), Kernel::Glds, 838, 512, 8);
+    expect("commit 14000", level(14000), Kernel::Glds, 875, 64, 1);  // 875 -> 4 x 16 = 64, 292 -> 2 x 48 = 96
+    expect("commit 140", level(140), Kernel::Wide, 140, 256);
+    const Plan m8 = level(1400);
+    expect("commit 1400", m8, Kernel::WideMulti, 175, 256);
+    expect_true("commit 1400 shape", m8.multi.bpw == 8 && m8.multi.ring == 4 && m8.multi.chunk == 256 && !m8.multi.dbl);
+    expect("commit 1500", level(1500), Kernel::WideMulti, 188, 256);
+    expect("commit 375", level(375), Kernel::WideMulti, 75, 256);
+    expect("commit 1125", level(1125), Kernel::WideMulti, 225, 256);
+    expect("commit 6000", level(6000), Kernel::Quad, 94, 256);
+    expect("commit 9000", level(9000), Kernel::Quad, 141, 256);
+    // an arena off 16 bytes: no LDS-DMA levels
+    expect("commit 12000 unaligned", level(12000, false), Kernel::Quad, 188, 256);
+    expect("commit 1500 unaligned", level(1500, false), Kernel::WideMulti, 188, 256);
     expect("commit 9984 ncu=0", level(9984, true, 0), Kernel::Quad, 156, 256);
     expect("commit 16384 ncu=0", level(16384, true, 0), Kernel::Glds, 128, 512, 8);
 }
@@ -169,6 +215,21 @@ static void pointer_levels() {
     expect("pointer 257 x 10", level(257, 10), Kernel::Quad, 5, 256);
     expect("pointer 10 x 2000", level(10, 2000), Kernel::Quad, 1, 256);  // a 50,000-byte node does not fit the LDS
     expect("pointer 257 x 1200 ncu=0", level(257, 1200, 0), Kernel::PointerPc, 17, 128, 1);
+    // kNodeLds: 1,310 children are 32,752 bytes, 1,311 are 32,776 and take the quad even for one node
+    expect_true("node sizes", plan_pointer_block_size(1310) == 32752 && plan_pointer_block_size(1311) == 32776 &&
+                                  plan_pointer_block_size(2) == 56 && plan_pointer_block_size(1) == 32);
+    expect("pointer 1 x 1310", level(1, 1310), Kernel::Wide, 1, 256);
+    expect("pointer 2 x 1310", level(2, 1310), Kernel::Wide, 2, 256);
+    expect("pointer 1 x 1311", level(1, 1311), Kernel::Quad, 1, 256);
+    expect("pointer 2 x 1311", level(2, 1311), Kernel::Quad, 1, 256);
+    expect("pointer 258 x 1311", level(258, 1311), Kernel::Quad, 5, 256);
+    expect("pointer 2 x 4096", level(2, 4096), Kernel::Quad, 1, 256);
+    expect("pointer 2 x 65536", level(2, 65536), Kernel::Quad, 1, 256);
+    expect("pointer 513 x 2", level(513, 2), Kernel::Quad, 9, 256);
+    expect("pointer 129 x 2", level(129, 2), Kernel::Wide, 129, 256);
+    expect("pointer 258 x 41", level(258, 41), Kernel::Quad, 5, 256);
+    expect("pointer 300 x 1", level(300, 1), Kernel::Quad, 5, 256);
+    expect("pointer 7 x 1", level(7, 1), Kernel::Wide, 7, 256);
 }
 
 static void key_tags() {
@@ -196,6 +257,13 @@ static void key_tags() {
     expect_true("keys base+8", is(plan_key_tags(48, 48, 1000, false, false, 8), 0, 0, false, 0, 0, 1000, 4));
     expect_true("keys gathered", is(plan_key_tags(48, 48, 1000, true, false, 0), 0, 0, false, 0, 0, 1000, 4));
     expect_true("keys with lengths", is(plan_key_tags(48, 48, 1000, false, true, 0), 0, 0, false, 0, 0, 1000, 4));
+    // 1,223 keys = 19 batches (3 waves, one workgroup) and 7 keys for the lane kernel
+    expect_true("keys 256/256 n=1223", is(keys(256, 256, 1223), 19, 16, true, 1, 131072, 7, 1));
+    expect_true("keys 240/100 n=1223", is(keys(240, 100, 1223), 19, 15, false, 1, 122880, 7, 1));
+    expect_true("keys 96/0 n=1223", is(keys(96, 0, 1223), 19, 6, false, 1, 49152, 7, 1));
+    expect_true("keys stride 72", is(keys(72, 72, 1223), 0, 0, false, 0, 0, 1223, 5));
+    expect_true("keys 80/80 n=63", is(keys(80, 80, 63), 0, 0, false, 0, 0, 63, 1));
+    expect_true("keys 2^24+4133 at 256", is(keys(256, 256, (1u << 24) + 4133), 262208, 16, true, 8194, 131072, 37, 1));
     expect_true("keys 2^40", keys(48, 48, uint64_t{1} << 40).too_large);
 }
 

@@ -201,13 +201,15 @@ def test_device_commit_random_forests(dev, n, fanout, slot, how):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [12000, 20000, 36864])
+@pytest.mark.parametrize("n", [12000, 20000, 24576, 32768, 36864])
 def test_device_commit_streaming_level_mixed_lengths(dev, n):
     """Levels from 39 blocks per CU take the LDS-DMA commit kernel (on 256 CUs: 12,000
     leaves in 3-wave workgroups, 20,000 in 1-wave ones, 36,864 in 3-wave ones again
-    where 8-wave ones would put two workgroups on some CUs): leaves of mixed storm lengths
-    (workgroups whose blocks run out of stripes at different tiles), a third relocating,
-    shuffled dirty list; vs the oracle's serial commit."""
+    where 8-wave ones would put two workgroups on some CUs; 24,576 = kBigBatch, where the
+    3/4 rule still gives 3-wave workgroups, and 32,768 in 8-wave ones,
+    k_commit_level_glds<16, 2, 8>: tests/cpp/dispatch_plan_test.cpp pins these plans):
+    leaves of mixed storm lengths (workgroups whose blocks run out of stripes at different
+    tiles), a third relocating, shuffled dirty list; vs the oracle's serial commit."""
     rng = np.random.default_rng(n)
     slot = 32768
     lens = rng.choice([72, 28808, 30000, 31808, 32768, 4097, 512], size=n)
@@ -223,10 +225,80 @@ def test_device_commit_streaming_level_mixed_lengths(dev, n):
     bp["parent"][has] = inv[bp["parent"][has]]
     ref_arena, ref_b = arena.copy(), bp.copy()
     want_cs, want_last = o.commit(ref_arena, ref_b, 4, last)
+    assert_inside(bp, arena.size)
     out, cs, last2 = device_commit(arena, bp, 4, last, dev)
     assert np.array_equal(cs, want_cs)
     assert np.array_equal(bp["address"], ref_b["address"]) and last2 == want_last
     assert np.array_equal(out, ref_arena)
+
+
+def assert_inside(b, nbytes, shift=0):
+    """Every byte range the commit reads or writes lies inside an arena of nbytes: blocks,
+    24-byte origin Pointers and origin type bytes (`shift`: bytes before the arena)."""
+    assert int((b["data_offset"] + b["length"]).max()) + shift <= nbytes
+    has = b["origin_pointer"] != np.uint64(sc.NO_ORIGIN)
+    assert int(b["origin_pointer"][has].max()) + 24 + shift <= nbytes
+    assert int(b["origin_type"][has].max()) + 1 + shift <= nbytes
+
+
+def _fast_random_bytes(rng, nbytes):
+    return rng.integers(0, 1 << 63, size=(nbytes + 7) // 8, dtype=np.int64).view(np.uint8)[:nbytes]
+
+
+@pytest.mark.gpu
+def test_device_commit_growing_chunks_of_long_leaves(dev):
+    """140,000 leaves of up to 8,192 bytes (past kVarMinLen, 16-byte aligned slots) under
+    fan-out 10: level 0 runs under the growing chunk schedule as two LDS-DMA launches, 32,768
+    and 107,232 leaves, both in 8-wave workgroups on 256 CUs (k_commit_level_glds<16, 2, 8>);
+    the 14,000 pointer blocks of 256 bytes above them, shorter than one 512-byte tile row,
+    take the same kernel in 1-wave workgroups; then 1,400 (k_commit_level_multi, 8 per
+    workgroup), 140, 14, 2 and 1 (k_commit_level_wide). Byte for byte with the oracle."""
+    n, fanout, slot, rev = 140000, 10, 8192, 5
+    rng = np.random.default_rng(140000)
+    lens = rng.choice([8192, 8191, 8176, 4097, 4096, 6000, 1000, 513, 512, 72, 0], size=n)
+    b, size, last = sc.pointer_forest(n, lens, fanout, slot=slot, revision=rev, first_address=1 << 33)
+    b["birth_revision"][rng.random(len(b)) < 0.3] = 2
+    arena = np.zeros(size, dtype=np.uint8)
+    arena[slot:slot + n * slot] = _fast_random_bytes(rng, n * slot)
+    bp = arrange(b, "upper_shuffled", rng)
+    ref_arena, ref_b = arena.copy(), bp.copy()
+    want_cs, want_last = o.commit(ref_arena, ref_b, rev, last)
+    assert_inside(bp, arena.size)
+    out, cs, last2 = device_commit(arena, bp, rev, last, dev)
+    assert np.array_equal(cs, want_cs)
+    assert np.array_equal(bp["address"], ref_b["address"]) and np.array_equal(bp["birth_revision"], ref_b["birth_revision"])
+    assert last2 == want_last
+    assert np.array_equal(out, ref_arena)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [1500, 12000])
+def test_device_commit_on_an_arena_base_off_16_bytes(dev, n):
+    """The arena starts 8 bytes into a 16-byte aligned allocation, which sets the `misaligned`
+    flag of stormck_commit_device although every data_offset is a multiple of 16: no LDS-DMA
+    levels. On 256 CUs 1,500 leaves take k_commit_level_multi (8-byte aligned starts are
+    staged), 12,000 the register quad k_commit_level where an aligned arena would take
+    k_commit_level_glds; the pointer blocks k_commit_level_wide."""
+    rng = np.random.default_rng(n + 8)
+    slot, rev = 32768, 9
+    lens = rng.choice([72, 28808, 30000, 31808, 32768, 4097], size=n)
+    b, size, last = sc.pointer_forest(n, lens, 1200, slot=slot, revision=rev, first_address=100)
+    b["birth_revision"][rng.random(len(b)) < 0.4] = 3
+    arena = np.zeros(size, dtype=np.uint8)
+    arena[slot:slot + n * slot] = _fast_random_bytes(rng, n * slot)
+    bp = arrange(b, "shuffled", rng)
+    ref_arena, ref_b = arena.copy(), bp.copy()
+    want_cs, want_last = o.commit(ref_arena, ref_b, rev, last)
+    d = torch.zeros(size + 16, dtype=torch.uint8, device=dev)
+    d[8:8 + size] = torch.from_numpy(arena).to(dev)
+    assert d.data_ptr() % 16 == 0
+    assert_inside(bp, d.numel(), shift=8)
+    cs, last2 = sc.commit_device(d.data_ptr() + 8, bp, rev, last)
+    out = d.cpu().numpy()
+    assert np.array_equal(cs, want_cs)
+    assert np.array_equal(bp["address"], ref_b["address"]) and np.array_equal(bp["birth_revision"], ref_b["birth_revision"])
+    assert last2 == want_last
+    assert np.array_equal(out[8:8 + size], ref_arena) and not out[:8].any() and not out[8 + size:].any()
 
 
 @pytest.mark.gpu

@@ -49,10 +49,21 @@ def _case(seed):
     return rng, n, mode, length, lens, stride, shift
 
 
-@pytest.mark.parametrize("seed", range(49))
+FIRST_SEEDS = 49  # cases 0..48 are as they always were; later seeds also toss the gather coin below
+
+
+def _uniform_gather(seed, mode):
+    """Gathered offsets with one length for all blocks and no lens pointer (OFFS without LENS):
+    a coin of its own generator, so that no draw of _case's stream moves."""
+    return mode == "gather" and seed >= FIRST_SEEDS and bool(np.random.default_rng(7000 + seed).integers(0, 2))
+
+
+@pytest.mark.parametrize("seed", range(FIRST_SEEDS + 21))
 def test_dispatch_fuzz(dev, seed):
     from storm_amd import engine
     rng, n, mode, length, lens, stride, shift = _case(seed)
+    if _uniform_gather(seed, mode):
+        lens = None
     size = shift + n * stride + 64
     host = rng.integers(0, 256, size=size, dtype=np.uint8)
     d = torch.from_numpy(host).to(dev)
@@ -61,12 +72,15 @@ def test_dispatch_fuzz(dev, seed):
     d_lens = torch.from_numpy(lens.view(np.int32)).to(dev) if lens is not None else None
     lp = d_lens.data_ptr() if d_lens is not None else 0
     if mode == "gather":
+        longest = int(lens.max()) if lens is not None else length
         offs = (np.arange(n, dtype=np.uint64) * stride + shift
-                + rng.integers(0, max(1, stride - int(lens.max()) + 1), size=n).astype(np.uint64))
+                + rng.integers(0, max(1, stride - longest + 1), size=n).astype(np.uint64))
+        assert int(offs.max()) + longest <= d.numel()
         d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
-        engine.checksum_gather_device(d.data_ptr(), d_offs.data_ptr(), n, out.data_ptr(), 0, lp)
-        want = np.array([o.xxh64(host[int(offs[i]):int(offs[i]) + int(lens[i])]) for i in range(n)],
-                        dtype=np.uint64)
+        engine.checksum_gather_device(d.data_ptr(), d_offs.data_ptr(), n, out.data_ptr(), 0 if lens is not None else length,
+                                      lp)
+        want = np.array([o.xxh64(host[int(offs[i]):int(offs[i]) + (int(lens[i]) if lens is not None else length)])
+                         for i in range(n)], dtype=np.uint64)
     else:
         engine.checksum_device(base, stride, n, out.data_ptr(), length, lp)
         want = o.checksum_batch(host[shift:], n, stride, length, lens=lens, threads=8)
@@ -87,3 +101,42 @@ def test_dispatch_fuzz(dev, seed):
     torch.cuda.synchronize()
     first = int(idx[0]) if k else n
     assert res.cpu().numpy().view(np.uint64).tolist() == [first, k], (seed, n, mode, length, stride, shift)
+
+
+def _offs_only_classes():
+    """(name, n) per dispatch class of an offsets-only gather, from the thresholds of
+    plan_checksum (dispatch.h) at this device's CU count: kWideBatch, kMultiBpw and
+    kMultiBpwRing per CU, one wave (16 blocks) per CU, and the first size past it."""
+    from storm_amd import engine
+    cu = engine._cu_count()
+    assert 5 * cu > 128
+    return [("Wide", 128), ("WideMulti 5", 5 * cu), ("WideMulti 8", 5 * cu + 1), ("WideMulti 8", 8 * cu),
+            ("QuadSpread", 8 * cu + 1), ("QuadSpread", 16 * cu), ("Quad", 16 * cu + 1)]
+
+
+@pytest.mark.parametrize("length", [33, 4099, 9001])
+def test_offsets_only_gather_reaches_every_small_class(dev, length):
+    """OFFS without LENS, which the fuzz above meets only by chance: k_xxh64_wide<false, true>
+    (128 blocks), k_xxh64_wide_multi<false, true, ., 5> (5 per CU) and <., 8> (one more, and 8
+    per CU), the one-wave k_xxh64_quad<., false, true> (up to 16 per CU) and the 256-thread one
+    (one block more: still fewer than kMidBatch blocks, so not k_xxh64_glds_var). Lengths of
+    one stripe and a byte, one 4 KiB ring chunk and three bytes, and three chunks. Blocks
+    start at any byte alignment, in shuffled order; every block is compared with the oracle."""
+    from storm_amd import engine
+    rng = np.random.default_rng(length)
+    classes = _offs_only_classes()
+    n_max = max(n for _, n in classes)
+    assert n_max < 10240  # kMidBatch: below it no gather takes the LDS-DMA kernel
+    slot = length + 29
+    host = rng.integers(0, 256, size=n_max * slot + 64, dtype=np.uint8)
+    d = torch.from_numpy(host).to(dev)
+    for name, n in classes:
+        offs = rng.permutation(n_max)[:n].astype(np.uint64) * np.uint64(slot) + rng.integers(0, 30, size=n).astype(np.uint64)
+        assert int(offs.max()) + length <= d.numel()
+        d_offs = torch.from_numpy(offs.view(np.int64)).to(dev)
+        out = torch.zeros(n, dtype=torch.int64, device=dev)
+        engine.checksum_gather_device(d.data_ptr(), d_offs.data_ptr(), n, out.data_ptr(), length)
+        torch.cuda.synchronize()
+        want = o.checksum_gather(host, offs, length)
+        bad = np.nonzero(out.cpu().numpy().view(np.uint64) != want)[0]
+        assert len(bad) == 0, (name, n, length, bad[:8])

@@ -712,6 +712,53 @@ def test_key_tags_f4(dev):
             assert np.array_equal(_u64(o2), o.checksum_batch(k2, m, stride, klen)), (stride, klen)
 
 
+def _key_tags_vs_oracle(dev, keys, base_shift, stride, klen, n):
+    """Tags of n keys of klen bytes, stride apart, from base_shift bytes into `keys` (a flat
+    host array), against the oracle; the range is checked on the host before the launch."""
+    from oracle import oracle as o
+    from storm_amd import engine
+    d = _to_dev(keys, dev)
+    assert n >= 1 and klen <= stride and base_shift + (n - 1) * stride + klen <= d.numel()
+    out = torch.zeros(n, dtype=torch.int64, device=dev)
+    engine.key_tags_device(d.data_ptr() + base_shift, n, out.data_ptr(), stride=stride, length=klen)
+    torch.cuda.synchronize()
+    return np.array_equal(_u64(out), o.checksum_batch(keys[base_shift:], n, stride, klen))
+
+
+@pytest.mark.parametrize("stride", [80, 96, 112, 128, 160, 192, 240, 256])
+def test_key_tags_runtime_stride_kernel(dev, stride):
+    """k_key_tags_lds (strides 80..256, 16-byte aligned base, n >= 64): every key length
+    0..stride, so every tail shape of finish_lds16 below and at the stride; n = two whole
+    waves of 8 batches, a partial wave of 3 batches, and 7 keys left for k_key_tags."""
+    from oracle import oracle as o
+    from storm_amd import engine
+    n = 64 * (8 * 2 + 3) + 7
+    keys = np.random.default_rng(stride).integers(0, 256, size=n * stride, dtype=np.uint8)
+    d = _to_dev(keys, dev)
+    assert d.data_ptr() % 16 == 0 and n * stride <= d.numel()
+    out = torch.zeros(n, dtype=torch.int64, device=dev)
+    for klen in range(0, stride + 1):
+        engine.key_tags_device(d.data_ptr(), n, out.data_ptr(), stride=stride, length=klen)
+        torch.cuda.synchronize()
+        got, want = _u64(out), o.checksum_batch(keys, n, stride, klen)
+        bad = np.nonzero(got != want)[0]
+        assert len(bad) == 0, (stride, klen, bad[:8])
+
+
+def test_key_tags_fall_backs_to_the_lane_kernel(dev):
+    """What plan_key_tags sends to k_key_tags<false, false> alone: a base that is not 16-byte
+    aligned, strides that are no multiple of 16, fewer than 64 keys; and 64 keys exactly,
+    which are one ring batch with no lane-kernel launch after it."""
+    rng = np.random.default_rng(4872)
+    keys = rng.integers(0, 256, size=8 + 1223 * 80, dtype=np.uint8)
+    for shift, stride, klen, n in [(8, 48, 48, 1223), (8, 48, 31, 1223),        # base + 8
+                                   (0, 40, 40, 1223), (0, 40, 17, 1000), (0, 72, 72, 1223), (0, 72, 9, 999),
+                                   (0, 48, 48, 1), (0, 48, 48, 63), (0, 80, 80, 63), (0, 256, 256, 1),
+                                   (0, 48, 48, 64), (0, 48, 20, 64), (0, 80, 80, 64), (0, 80, 33, 64),
+                                   (0, 256, 256, 64)]:
+        assert _key_tags_vs_oracle(dev, keys, shift, stride, klen, n), (shift, stride, klen, n)
+
+
 def test_read_verify_fd_f2(dev, tmp_path):
     """f2/f3: batched cold read + verify from a file device (cache.fetchBlock =
     Store.ReadBlock + VerifyChecksum, cache/cache.go:139-167): data lands in the
