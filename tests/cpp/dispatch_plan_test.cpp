@@ -158,6 +158,9 @@ static void lengths_and_gathers() {
     expect("gather+lens n=11264 bound 4200", plan(short_gather(11264, 4200, true)), Kernel::GldsVar, 235, 192, 3);
     expect("gather+lens n=12289 bound 4200", plan(short_gather(12289, 4200, true)), Kernel::GldsVar, 769, 64, 1);
     expect("gather n=11264 len=4096", plan(short_gather(11264, 4096, false)), Kernel::Quad, 176, 256);
+    // a scrub level of 11,300 leaves and two pointer blocks (tests/test_scrub_damage_gpu.py): offsets and
+    // lengths bounded by 32 KiB; 707 one-wave workgroups -> 3 x 16 and 236 three-wave ones -> 48: the tie
+    expect("scrub level n=11302", plan(short_gather(11302, 32768, true)), Kernel::GldsVar, 236, 192, 3);
     // strided rows 512 KiB apart, 4,099 bytes each
     auto far_rows = [](uint64_t n) {
         Query q = uniform(n, 4099);

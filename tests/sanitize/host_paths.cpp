@@ -11,6 +11,8 @@
 //     caller threads at once, and the routed batch with a device;
 //   * f1 commit planning: validation, the threaded height walk-up (ForkJoin pool),
 //     cycle / range / alignment errors, on shuffled forests up to 300K records;
+//   * the scrub's host leg (stormck_scrub_tree_host) over a forest that stormck_commit_host
+//     committed, on 1 and 5 threads with a reachable bitmap, intact and damaged;
 //   * with a gfx950 device (GPU box): the same commits run to completion on a device
 //     arena and are compared with the oracle's serial commit; the host pipeline
 //     (pageable and registered sources, parallel staging copies, both stages), the
@@ -280,6 +282,64 @@ static void commit_host_leg(bool device) {
             for (int it = 0; it < 3; ++it) one(3000 + 977 * t, t & 1, (it == 2) ? 7u : 0u, 50 + 10 * t + it);
         });
     for (auto& x : th) x.join();
+}
+
+// The scrub's host leg (no device needed): a forest with nothing relocated and one leaf
+// length, committed by stormck_commit_host, is an image of `slot`-byte blocks whose root the
+// commit left in the singularity's SpacePointer. stormck_scrub_tree_host walks it on 1 and 5
+// threads with a reachable bitmap: intact, then with three flipped leaves and one entry whose
+// address is n_blocks (the path above that entry re-hashed, so only the entry is wrong).
+static void scrub_host_leg() {
+    std::mt19937_64 rng(31);
+    const uint64_t nl = 1500, slot = 1024;
+    const uint32_t fanout = 10, leaf_len = 728;
+    Forest f = make_forest(nl, fanout, slot, 5, rng, false);
+    const uint64_t n = f.b.size(), n_blocks = n + 1, n_pointer = n - nl;
+    for (auto& r : f.b) {
+        r.birth_revision = 6;  // born in this revision: the commit relocates nothing
+        if (r.type == STORMCK_LEAF_BLOCK) r.length = leaf_len;
+    }
+    std::vector<uint8_t> host(f.arena_bytes, 0);
+    for (uint64_t i = 0; i < nl; ++i)
+        for (uint32_t k = 0; k < leaf_len; ++k) host[f.b[i].data_offset + k] = static_cast<uint8_t>(rng());
+    std::vector<uint64_t> cs(n, 0);
+    uint64_t last = f.last;
+    CHECK(stormck_commit_host(host.data(), f.b.data(), n, 5, &last, cs.data(), 0) == STORMCK_OK && last == f.last);
+    const stormck_scrub_layout lay{slot, n_blocks, fanout, 10, 536, leaf_len};
+    auto walk = [&](uint32_t threads, stormck_scrub_report* rep, uint64_t* reached) {
+        stormck_pointer root;
+        std::memcpy(&root, host.data() + 32, sizeof root);
+        std::vector<uint32_t> bitmap((n_blocks + 31) / 32, 0xffffffffu);
+        const int rc = stormck_scrub_tree_host(host.data(), &lay, &root, host[56], STORMCK_SCRUB_BLOB, leaf_len,
+                                               bitmap.data(), rep, threads);
+        *reached = 0;
+        for (uint32_t w : bitmap) *reached += static_cast<uint64_t>(__builtin_popcount(w));
+        return rc;
+    };
+    for (uint32_t threads : {1u, 5u}) {
+        stormck_scrub_report rep;
+        uint64_t reached = 0;
+        CHECK(walk(threads, &rep, &reached) == STORMCK_OK);
+        CHECK(rep.verified[STORMCK_SCRUB_POINTER] == n_pointer && rep.verified[STORMCK_SCRUB_BLOB] == nl);
+        CHECK(rep.n_mismatch == 0 && rep.n_structural == 0 && rep.first_error == STORMCK_SCRUB_OK && rep.levels == 5);
+        CHECK(rep.bytes_hashed == n_pointer * 256 + nl * leaf_len && reached == n_blocks);
+    }
+    for (uint64_t leaf : {uint64_t{57}, uint64_t{700}, uint64_t{1499}}) host[f.b[leaf].data_offset + 100] ^= 1;
+    const uint64_t lost = 41;  // leaf 41 (address 42): slot 1 of the fifth pointer block of the level above
+    std::memcpy(host.data() + f.b[lost].origin_pointer + 8, &n_blocks, 8);
+    for (int64_t i = f.b[lost].parent; i >= 0; i = f.b[i].parent) {
+        const uint64_t sum = stormck_xxh64(host.data() + f.b[i].data_offset, f.b[i].length);
+        std::memcpy(host.data() + f.b[i].origin_pointer, &sum, 8);  // the top block's origin is the singularity
+    }
+    for (uint32_t threads : {1u, 5u}) {
+        stormck_scrub_report rep;
+        uint64_t reached = 0;
+        CHECK(walk(threads, &rep, &reached) == STORMCK_EMISMATCH);
+        CHECK(rep.verified[STORMCK_SCRUB_POINTER] == n_pointer && rep.verified[STORMCK_SCRUB_BLOB] == nl - 4);
+        CHECK(rep.n_mismatch == 3 && rep.n_structural == 1 && rep.levels == 5 && reached == n_blocks - 1);
+        CHECK(rep.first_error == STORMCK_SCRUB_RANGE && rep.first_level == 4 && rep.first_address == n_blocks);
+        CHECK(rep.first_parent == nl + 1 + lost / fanout && rep.first_slot == lost % fanout);
+    }
 }
 
 // The batch host leg (no device needed): stormck_checksum_host_leg / _verify_host_leg on
@@ -594,6 +654,8 @@ int main() {
     std::printf("commit host leg: done\n");
     batch_host_leg(device);
     std::printf("batch host leg: done\n");
+    scrub_host_leg();
+    std::printf("scrub host leg: done\n");
     if (device) host_pipeline_paths();
     if (device) concurrent_callers();
     if (device) std::printf("concurrent callers: done\n");
