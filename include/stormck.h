@@ -371,9 +371,11 @@ typedef struct stormck_dirty_block {
  * Synchronous on `stream`. Any children-first order is a valid storm commit order
  * (storm's own order follows Go map iteration); this one is deterministic.
  * Argument errors (parent range, origin alignment, cycles) and a missing device are
- * reported before anything is changed. A HIP failure part-way leaves the commit
- * partly applied, as storm's own loop does on a write error; *last_allocated_block
- * then still matches the relocations already written into blocks. */
+ * reported before anything is changed; of several defects every leg reports the one of the
+ * lowest block whose check or walk to the root fails (any of them on several threads). A
+ * HIP failure part-way leaves the commit partly applied, as storm's own loop does on a
+ * write error; *last_allocated_block then still matches the relocations already written
+ * into blocks. */
 int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
                           uint64_t* last_allocated_block, uint64_t* out_checksums, void* stream);
 
@@ -447,7 +449,8 @@ int stormck_route_devices(const int* devices, int n_devices);
  * STORMCK_MEM_PAGEABLE or STORMCK_MEM_PINNED (page-locked; for a commit, registered);
  * n_devices: devices the call could use (0: host leg only). *leg = the leg the routed call
  * would take (STORMCK_LEG_NONE for n == 0); predicted_us (optional, 3 doubles): host,
- * device and split time, INFINITY where the leg cannot run or the split gains nothing. */
+ * device and split time, INFINITY where the leg cannot run or the split gains nothing. A forest
+ * that the commit's legs would refuse (stormck_commit_device) is STORMCK_EINVAL here too. */
 #define STORMCK_MEM_PAGEABLE 0u
 #define STORMCK_MEM_PINNED 1u
 int stormck_route_plan_batch(uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, uint32_t memory,

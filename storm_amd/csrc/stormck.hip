@@ -30,6 +30,7 @@
 #include <rccl/rccl.h>  // types and declarations only: RCCL is loaded at run time (multi_root.h)
 
 #include "../../include/stormck.h"
+#include "commit_plan.h"
 #include "dispatch.h"
 #include "kernels.h"
 #include "xxh64_host.h"
@@ -1689,93 +1690,48 @@ int stormck_key_tags_device(const void* d_keys, uint64_t stride, const uint64_t*
 }
 
 
-int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
-                          uint64_t* last_allocated_block, uint64_t* out_checksums, void* stream) {
-    static_assert(sizeof(stormck_dirty_block) == 56, "stormck_dirty_block ABI");
-    if (n == 0) return STORMCK_OK;
-    if (!d_arena || !blocks || !last_allocated_block || !out_checksums) return fail(STORMCK_EINVAL, "null argument");
-    if (n > 0xffffffffULL) return fail(STORMCK_EINVAL, "more than 2^32 dirty blocks");
-    PhaseTimer pt("commit");
+}  // extern "C" (the commit's legs and the routing engine below are internal C++)
+
+namespace {
+
+// commit_plan.h's executor on the pool: fn(t, lo, hi) over contiguous ranges of [0, count)
+// on min(cap, pool, count / grain + 1) threads.
+struct PoolPar {
+    unsigned cap;
+    uint64_t grain;
+    template <class F>
+    unsigned operator()(uint64_t count, F&& fn) const {
+        if (cap <= 1 || count < grain) {  // storm's small commits: no pool, not even its lock
+            fn(0u, uint64_t{0}, count);
+            return 1;
+        }
+        ForkJoin& fj = ForkJoin::get();
+        const unsigned nt = static_cast<unsigned>(std::min<uint64_t>({cap, kMaxParts, fj.size(), count / grain + 1}));
+        fj.run(nt, [&](unsigned t) { fn(t, count * t / nt, count * (t + 1) / nt); });
+        return nt;
+    }
+};
+// The planning passes (heights, the order) and the record staging, on at most `threads`
+// pool threads (0 = the pool).
+PoolPar plan_par(uint32_t threads = 0) { return {threads ? threads : kMaxParts, 16384}; }  // the pool has at most 16
+PoolPar stage_par(uint32_t threads = 0) { return {threads ? std::min(threads, 8u) : 8u, 8192}; }
+
+// Validation and heights of a commit, the same for every leg; nothing is changed.
+int commit_forest(const stormck_dirty_block* blocks, uint64_t n, uint64_t revision, uint32_t threads, Heights* H) {
+    const CommitError e = commit_heights(blocks, n, revision, plan_par(threads), H);
+    if (e == CommitError::Ok) return STORMCK_OK;
+    return fail(e == CommitError::NoMem ? STORMCK_ENOMEM : STORMCK_EINVAL, commit_error_message(e));
+}
+
+// The device leg of a planned commit: the level kernels read and write d_arena in place.
+int commit_device_run(void* d_arena, stormck_dirty_block* blocks, const Heights& H, uint64_t revision,
+                      uint64_t* last_allocated_block, uint64_t* out_checksums, void* stream, PhaseTimer& pt) {
     ForkJoin& fj = ForkJoin::get();
-    const unsigned nt = static_cast<unsigned>(std::min<uint64_t>(fj.size(), n / 16384 + 1));
-    // fn(t, lo, hi) on nt pool threads over contiguous ranges of [0, n)
-    auto par = [&](auto&& fn) { fj.run(nt, [&](unsigned t) { fn(t, n * t / nt, n * (t + 1) / nt); }); };
-    // Pass 1 (the only pass before the first launch): validate, and raise every
-    // ancestor's height to >= its distance above each block (atomic max; a walk stops at
-    // the first ancestor some walk has already raised high enough, which then carries
-    // the raise further up). The first raise of a block from 0 marks it as an upper
-    // block; their count and smallest index tell whether level 0 (the blocks without
-    // dirty children) is a prefix of the caller's array.
-    std::unique_ptr<uint32_t, void (*)(void*)> height_mem(static_cast<uint32_t*>(std::calloc(n, 4)), std::free);
-    if (!height_mem) return fail(STORMCK_ENOMEM, "commit: height array");
-    uint32_t* height = height_mem.get();
-    std::atomic<int> bad{0};  // 1 parent range, 2 origin alignment, 3 cycle
-    std::atomic<uint64_t> relocating_n{0}, upper_n{0}, upper_min{n};
-    std::atomic<bool> misaligned{(reinterpret_cast<uintptr_t>(d_arena) & 15) != 0};
-    std::atomic<uint32_t> longest{0};  // the longest block: short-block forests skip the LDS-DMA levels
-    par([&](unsigned, uint64_t lo, uint64_t hi) {
-        uint64_t reloc = 0, up = 0, up_min = n;
-        uint32_t my_longest = 0;
-        bool mis = false;
-        for (uint64_t i = lo; i < hi && !bad.load(std::memory_order_relaxed); ++i) {
-            const stormck_dirty_block& b = blocks[i];
-            mis |= (b.data_offset & 15) != 0;
-            my_longest = std::max(my_longest, b.length);
-            if (b.parent != STORMCK_NO_PARENT && (b.parent < 0 || static_cast<uint64_t>(b.parent) >= n)) {
-                bad.store(1);
-                break;
-            }
-            if (b.origin_pointer != STORMCK_NO_ORIGIN && ((b.origin_pointer & 7) != 0)) {
-                bad.store(2);
-                break;
-            }
-            reloc += b.birth_revision <= revision;
-            uint64_t cur = i;
-            uint32_t hh = 0;
-            while (blocks[cur].parent != STORMCK_NO_PARENT) {
-                const uint64_t p = static_cast<uint64_t>(blocks[cur].parent);
-                if (p >= n) {
-                    bad.store(1);
-                    break;
-                }
-                ++hh;
-                if (hh > n) {
-                    bad.store(3);
-                    break;
-                }
-                uint32_t old = __atomic_load_n(&height[p], __ATOMIC_RELAXED);
-                while (old < hh &&
-                       !__atomic_compare_exchange_n(&height[p], &old, hh, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
-                }
-                if (old >= hh) break;  // another walk holds p at >= hh and carries it upward
-                if (old == 0) {        // this walk raised p first
-                    ++up;
-                    up_min = std::min(up_min, p);
-                }
-                cur = p;
-            }
-        }
-        relocating_n.fetch_add(reloc, std::memory_order_relaxed);
-        upper_n.fetch_add(up, std::memory_order_relaxed);
-        uint64_t m = upper_min.load(std::memory_order_relaxed);
-        while (up_min < m && !upper_min.compare_exchange_weak(m, up_min, std::memory_order_relaxed)) {
-        }
-        if (mis) misaligned.store(true, std::memory_order_relaxed);
-        uint32_t cur = longest.load(std::memory_order_relaxed);
-        while (my_longest > cur && !longest.compare_exchange_weak(cur, my_longest, std::memory_order_relaxed)) {
-        }
-    });
-    if (bad.load() == 1) return fail(STORMCK_EINVAL, "parent index out of range");
-    if (bad.load() == 2) return fail(STORMCK_EINVAL, "origin_pointer must be 8-byte aligned (Go blocks.Pointer alignment)");
-    if (bad.load() == 3) return fail(STORMCK_EINVAL, "parent links form a cycle");
-    const uint64_t relocating = relocating_n.load();
-    const uint64_t nu = upper_n.load(), n0 = n - nu;
-    if (n0 == 0) return fail(STORMCK_EINVAL, "parent links form a cycle");  // every block has a dirty child
-    const bool prefix0 = nu == 0 || upper_min.load() == n0;
+    const uint64_t n = H.n, nu = H.n_upper, n0 = H.n0();
     // the LDS-DMA level kernels need 16-byte aligned rows, and pay only when blocks are
     // longer than a few of their 512-byte rows (as launch_checksum's kVarMinLen)
-    const bool glds_levels = !misaligned.load() && longest.load() > knobs().var_min_len;
-    pt.mark("heights");
+    const bool glds_levels =
+        (reinterpret_cast<uintptr_t>(d_arena) & 15) == 0 && !H.data_off16 && H.longest > knobs().var_min_len;
 
     // device resources before the records are touched: a failure here leaves them as given
     DeviceCtx* c = nullptr;
@@ -1805,28 +1761,12 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
     // within a height). `order` (commit position -> caller's index) is materialised only
     // when it is not the identity. Level 0's part is all the first launch needs; the
     // upper part is built while level 0 hashes.
-    std::vector<uint32_t> order;
-    std::vector<uint32_t> upper;  // upper blocks in index order (when level 0 is not a prefix)
-    if (!prefix0) {
-        order.resize(n);
-        upper.resize(nu);
-        std::vector<uint64_t> z(nt + 1, 0);
-        par([&](unsigned t, uint64_t lo, uint64_t hi) {
-            uint64_t m = 0;
-            for (uint64_t i = lo; i < hi; ++i) m += height[i] == 0;
-            z[t + 1] = m;
-        });
-        for (unsigned t = 0; t < nt; ++t) z[t + 1] += z[t];
-        par([&](unsigned t, uint64_t lo, uint64_t hi) {
-            uint64_t a = z[t], u = lo - z[t];
-            for (uint64_t i = lo; i < hi; ++i) {
-                if (height[i] == 0) order[a++] = static_cast<uint32_t>(i);
-                else upper[u++] = static_cast<uint32_t>(i);
-            }
-        });
+    CommitOrder O;
+    if (!H.prefix0()) {
+        order_level0(H, plan_par(), &O);
         pt.mark("order0");
     }
-    auto idx_at = [&](uint64_t k) -> uint64_t { return order.empty() ? k : order[k]; };
+    const std::vector<uint32_t>& order = O.order;
 
     hipStream_t st = static_cast<hipStream_t>(stream);
     const Knobs kn = commit_knobs();
@@ -1871,36 +1811,14 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
     // host moves a launch's checksums to the caller's order while later ones run.
     uint64_t last = *last_allocated_block;
     auto stage_records = [&](uint64_t a, uint64_t b) {
-        const uint64_t cnt = b - a;
-        stormck_dirty_block* dst = c->commit_rec + a;
-        const unsigned tn = static_cast<unsigned>(std::min<uint64_t>({8, fj.size(), cnt / 8192 + 1}));
-        if (!relocating && order.empty()) {
-            par_copy(reinterpret_cast<uint8_t*>(dst), reinterpret_cast<const uint8_t*>(blocks + a),
-                     cnt * sizeof(stormck_dirty_block), 1ULL << 20);
+        stormck_dirty_block* rec = c->commit_rec;
+        if (!H.relocating && order.empty()) {
+            par_copy(reinterpret_cast<uint8_t*>(rec + a), reinterpret_cast<const uint8_t*>(blocks + a),
+                     (b - a) * sizeof(stormck_dirty_block), 1ULL << 20);
             return;
         }
-        std::vector<uint64_t> rc_(tn + 1, 0);
-        if (relocating) {
-            fj.run(tn, [&](unsigned t) {
-                uint64_t m = 0;
-                for (uint64_t k = a + cnt * t / tn, e = a + cnt * (t + 1) / tn; k < e; ++k)
-                    m += blocks[idx_at(k)].birth_revision <= revision;
-                rc_[t + 1] = m;
-            });
-            for (unsigned t = 0; t < tn; ++t) rc_[t + 1] += rc_[t];
-        }
-        fj.run(tn, [&](unsigned t) {
-            uint64_t addr = last + rc_[t];
-            for (uint64_t k = a + cnt * t / tn, e = a + cnt * (t + 1) / tn; k < e; ++k) {
-                stormck_dirty_block& rec = blocks[idx_at(k)];
-                if (relocating && rec.birth_revision <= revision) {
-                    rec.address = ++addr;
-                    rec.birth_revision = revision + 1;
-                }
-                dst[k - a] = rec;
-            }
-        });
-        last += rc_[tn];
+        relocate_range(blocks, O, a, b, revision, H.relocating != 0, &last, stage_par(),
+                       [rec](uint64_t k, const stormck_dirty_block& r) { rec[k] = r; });
     };
     struct Back {
         uint64_t lo, cnt;
@@ -1918,16 +1836,14 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
         // workgroup per CU) starts the device after a small upload; each next chunk is 3x
         // the previous, small enough that its records (56 B per block over PCIe) arrive
         // before the previous chunk's blocks (~32 KiB each at HBM rate) are hashed.
-        uint64_t next = kn.commit_first, growth = kn.commit_growth;
         // A small commit (storm's per-revision commit: ~1,200 leaves under one pointer
         // block) returns its checksums in one piece after the last level: an event
         // recorded between two launches holds the second one back by about 4 us
         // (profiles/r02_c5_multi/), more than copying a few thousand checksums costs.
-        const bool one_piece = nu > 0 && n0 <= kCommitOnePiece;
+        const bool one_piece = commit_one_piece(nu, n0);
         uint64_t unsent = 0;  // first commit position not yet covered by `back`
-        for (uint64_t lo = 0; lo < n0;) {
-            uint64_t cnt = std::min(next, n0 - lo);
-            if (n0 - lo - cnt < kStreamBatch) cnt = n0 - lo;  // no runt last chunk
+        for (uint64_t lo = 0, cnt, next = kn.commit_first; lo < n0; lo += cnt, next = cnt * kn.commit_growth) {
+            cnt = level0_chunk(n0 - lo, next);
             stage_records(lo, lo + cnt);
             int e = launch_level(lo, cnt);
             if (e) return e;
@@ -1936,73 +1852,16 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
                 if (e) return e;
                 unsent = lo + cnt;
             }
-            lo += cnt;
-            next = cnt * growth;
         }
         pt.mark("level0_issue");
         if (nu == 0) return STORMCK_OK;
-        // Upper levels, planned while level 0 hashes: a stable counting sort by height of
-        // the upper blocks (index order within a height) unless already in that order.
-        auto uidx = [&](uint64_t u) -> uint32_t { return upper.empty() ? static_cast<uint32_t>(n0 + u) : upper[u]; };
-        const unsigned un = static_cast<unsigned>(std::min<uint64_t>(fj.size(), nu / 16384 + 1));
-        struct Part {
-            uint32_t max_h = 0;
-            bool sorted = true;
-            std::vector<uint64_t> hist;
-        };
-        std::vector<Part> part(un);
-        fj.run(un, [&](unsigned t) {
-            Part& P = part[t];
-            P.hist.assign(8, 0);
-            const uint64_t lo = nu * t / un, hi = nu * (t + 1) / un;
-            uint32_t prev = lo ? height[uidx(lo - 1)] : 0;
-            for (uint64_t u = lo; u < hi; ++u) {
-                const uint32_t h = height[uidx(u)];
-                P.sorted &= h >= prev;
-                prev = h;
-                if (h >= P.hist.size()) P.hist.resize(static_cast<size_t>(h) + 1, 0);
-                P.hist[h]++;
-                P.max_h = std::max(P.max_h, h);
-            }
-        });
-        uint32_t max_h = 0;
-        bool sorted = true;
-        for (const Part& P : part) {
-            max_h = std::max(max_h, P.max_h);
-            sorted &= P.sorted;
-        }
-        // level_start[h] = commit position of height h's first block (h >= 1)
-        std::vector<uint64_t> level_start(static_cast<size_t>(max_h) + 2, 0);
-        for (const Part& P : part)
-            for (size_t l = 1; l < P.hist.size() && l <= max_h; ++l) level_start[l + 1] += P.hist[l];
-        level_start[1] = n0;
-        for (uint32_t l = 1; l <= max_h; ++l) level_start[l + 1] += level_start[l];
-        if (!sorted || !upper.empty()) {
-            if (order.empty()) {
-                order.resize(n);
-                for (uint64_t k = 0; k < n0; ++k) order[k] = static_cast<uint32_t>(k);
-            }
-            if (sorted) {
-                std::memcpy(order.data() + n0, upper.data(), nu * 4);
-            } else {
-                std::vector<std::vector<uint64_t>> pos(un, std::vector<uint64_t>(level_start.begin(), level_start.end() - 1));
-                for (unsigned t = 1; t < un; ++t)
-                    for (size_t l = 1; l <= max_h; ++l)
-                        pos[t][l] = pos[t - 1][l] + (l < part[t - 1].hist.size() ? part[t - 1].hist[l] : 0);
-                fj.run(un, [&](unsigned t) {
-                    std::vector<uint64_t>& ps = pos[t];
-                    for (uint64_t u = nu * t / un, e = nu * (t + 1) / un; u < e; ++u) {
-                        const uint32_t i = uidx(u);
-                        order[ps[height[i]]++] = i;
-                    }
-                });
-            }
-        }
+        // Upper levels, planned while level 0 hashes.
+        order_upper(H, plan_par(), &O);
         pt.mark("order_upper");
         stage_records(n0, n);
         int e = STORMCK_OK;
-        for (uint32_t l = 1; l <= max_h; ++l) {
-            const uint64_t lo = level_start[l], cnt = level_start[l + 1] - lo;
+        for (uint32_t l = 1; l <= H.max_h; ++l) {
+            const uint64_t lo = O.level_start[l], cnt = O.level_start[l + 1] - lo;
             if (cnt == 0) continue;
             e = launch_level(lo, cnt);
             if (e) return e;
@@ -2040,7 +1899,7 @@ int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n
     return rc;
 }
 
-}  // extern "C" (the routing engine below is internal C++)
+}  // namespace
 
 // ---- routing of host-memory work: host, device and split legs ------------------------
 // Work that lives in host memory (storm's cache.data: the Go shim's ChecksumBatch,
@@ -2867,37 +2726,6 @@ LegPlan plan_batch(const stormck_route_rates& r, uint64_t n, const BatchShape& s
 }
 
 // ---- the commit cost model ----------------------------------------------------------
-struct CommitShape {
-    std::vector<uint64_t> cnt, bytes, longest;  // per height
-};
-
-// Heights of a dirty forest (children first); false: malformed (the legs report why).
-bool commit_shape(const stormck_dirty_block* blocks, uint64_t n, CommitShape* s) {
-    std::vector<uint32_t> height(n, 0);
-    for (uint64_t i = 0; i < n; ++i) {
-        uint64_t cur = i;
-        uint32_t hh = 0;
-        while (blocks[cur].parent != STORMCK_NO_PARENT) {
-            if (blocks[cur].parent < 0 || static_cast<uint64_t>(blocks[cur].parent) >= n || ++hh > n) return false;
-            cur = static_cast<uint64_t>(blocks[cur].parent);
-            if (height[cur] >= hh) break;
-            height[cur] = hh;
-        }
-    }
-    for (uint64_t i = 0; i < n; ++i) {
-        const uint32_t h = height[i];
-        if (h >= s->cnt.size()) {
-            s->cnt.resize(h + 1, 0);
-            s->bytes.resize(h + 1, 0);
-            s->longest.resize(h + 1, 0);
-        }
-        s->cnt[h]++;
-        s->bytes[h] += blocks[i].length;
-        s->longest[h] = std::max<uint64_t>(s->longest[h], blocks[i].length);
-    }
-    return true;
-}
-
 // One height on the host threads: its bytes at the threads' rate, at least one block's
 // chain, and a fork/join when it is spread.
 double host_height_us(const stormck_route_rates& r, const CommitShape& s, size_t l, unsigned nt) {
@@ -2936,61 +2764,25 @@ LegPlan plan_commit(const stormck_route_rates& r, const CommitShape& s, bool reg
 
 // ---- f1 on the host threads: the plan and the heights ---------------------------------
 struct CommitPlan {
-    std::vector<uint32_t> order;  // commit position -> the caller's index
-    std::vector<uint64_t> start;  // height h: commit positions [start[h], start[h + 1])
-    std::vector<uint64_t> off;    // commit position -> data_offset
-    std::vector<uint32_t> len;    // commit position -> length
+    CommitOrder O;              // the commit order and where each height starts in it
+    std::vector<uint64_t> off;  // commit position -> data_offset
+    std::vector<uint32_t> len;  // commit position -> length
 };
 
-// Validation, heights, the commit order (by height, index order within a height) and the
-// relocation in that order (cache/cache.go:114-118), with stormck_commit_device's rules and
-// messages; a failure changes nothing.
-int commit_plan(stormck_dirty_block* blocks, uint64_t n, uint64_t revision, uint64_t* last_allocated_block,
-                CommitPlan* P) {
-    if (n > 0xffffffffULL) return fail(STORMCK_EINVAL, "more than 2^32 dirty blocks");
-    std::vector<uint32_t> height(n, 0);
-    for (uint64_t i = 0; i < n; ++i) {
-        const stormck_dirty_block& b = blocks[i];
-        if (b.parent != STORMCK_NO_PARENT && (b.parent < 0 || static_cast<uint64_t>(b.parent) >= n))
-            return fail(STORMCK_EINVAL, "parent index out of range");
-        if (b.origin_pointer != STORMCK_NO_ORIGIN && (b.origin_pointer & 7) != 0)
-            return fail(STORMCK_EINVAL, "origin_pointer must be 8-byte aligned (Go blocks.Pointer alignment)");
-    }
-    uint32_t max_h = 0;
-    for (uint64_t i = 0; i < n; ++i) {
-        uint64_t cur = i;
-        uint32_t hh = 0;
-        while (blocks[cur].parent != STORMCK_NO_PARENT) {
-            cur = static_cast<uint64_t>(blocks[cur].parent);
-            if (++hh > n) return fail(STORMCK_EINVAL, "parent links form a cycle");
-            if (height[cur] >= hh) break;  // an earlier walk carries it upward
-            height[cur] = hh;
-            max_h = std::max(max_h, hh);
-        }
-    }
-    P->start.assign(static_cast<size_t>(max_h) + 2, 0);
-    for (uint64_t i = 0; i < n; ++i) P->start[height[i] + 1]++;
-    if (P->start[1] == 0) return fail(STORMCK_EINVAL, "parent links form a cycle");
-    for (uint32_t l = 0; l <= max_h; ++l) P->start[l + 1] += P->start[l];
-    P->order.resize(n);
-    {
-        std::vector<uint64_t> pos(P->start.begin(), P->start.end() - 1);
-        for (uint64_t i = 0; i < n; ++i) P->order[pos[height[i]]++] = static_cast<uint32_t>(i);
-    }
-    uint64_t last = *last_allocated_block;
-    P->off.resize(n);
-    P->len.resize(n);
-    for (uint64_t k = 0; k < n; ++k) {
-        stormck_dirty_block& b = blocks[P->order[k]];
-        if (b.birth_revision <= revision) {
-            b.address = ++last;
-            b.birth_revision = revision + 1;
-        }
-        P->off[k] = b.data_offset;
-        P->len[k] = b.length;
-    }
-    *last_allocated_block = last;
-    return STORMCK_OK;
+// The commit order of a validated forest and the relocation in that order, on at most
+// `threads` pool threads. Everything is allocated before the first record changes.
+void commit_plan(stormck_dirty_block* blocks, const Heights& H, uint64_t revision, uint64_t* last_allocated_block,
+                 uint32_t threads, CommitPlan* P) {
+    commit_order(H, plan_par(threads), &P->O);
+    P->off.resize(H.n);
+    P->len.resize(H.n);
+    uint64_t* off = P->off.data();
+    uint32_t* len = P->len.data();
+    relocate_range(blocks, P->O, 0, H.n, revision, H.relocating != 0, last_allocated_block, stage_par(threads),
+                   [off, len](uint64_t k, const stormck_dirty_block& r) {
+                       off[k] = r.data_offset;
+                       len[k] = r.length;
+                   });
 }
 
 // A height's checksums: the caller's out_checksums and, through the block's origin, the
@@ -2998,12 +2790,13 @@ int commit_plan(stormck_dirty_block* blocks, uint64_t n, uint64_t revision, uint
 struct CommitSink final : Sink {
     uint8_t* arena;
     const stormck_dirty_block* blocks;
-    const uint32_t* order;  // this height's slice of the commit order
+    const CommitOrder& O;
+    uint64_t lo;  // this height's first commit position
     uint64_t* out;
-    CommitSink(uint8_t* a, const stormck_dirty_block* b, const uint32_t* o, uint64_t* c)
-        : arena(a), blocks(b), order(o), out(c) {}
+    CommitSink(uint8_t* a, const stormck_dirty_block* b, const CommitOrder& o, uint64_t l, uint64_t* c)
+        : arena(a), blocks(b), O(o), lo(l), out(c) {}
     void one(uint64_t k, uint64_t h) override {
-        const uint64_t i = order[k];
+        const uint64_t i = O.at(lo + k);
         const stormck_dirty_block& b = blocks[i];
         out[i] = h;
         if (b.origin_pointer != STORMCK_NO_ORIGIN) {
@@ -3014,14 +2807,19 @@ struct CommitSink final : Sink {
     }
 };
 
-// The heights of a planned commit, children first: height 0 (the leaves) on the host
-// threads and `devs` at once (devices read the registered arena in place), every other
-// height on the host threads (they hold a few pointer blocks).
-int commit_heights(uint8_t* arena, stormck_dirty_block* blocks, const CommitPlan& P, uint64_t* out, unsigned nt,
-                   const std::vector<int>& devs, uint64_t device_leaves, uint64_t* device_done) {
+// The host and split legs of a validated commit: plan, then the heights, children first:
+// height 0 (the leaves) on the host threads and `devs` at once (devices read the registered
+// arena in place), every other height on the host threads (they hold a few pointer blocks).
+int commit_host_run(uint8_t* arena, stormck_dirty_block* blocks, const Heights& H, uint64_t revision,
+                    uint64_t* last_allocated_block, uint64_t* out, uint32_t threads, const std::vector<int>& devs,
+                    uint64_t device_leaves, uint64_t* device_done) {
+    CommitPlan P;
+    commit_plan(blocks, H, revision, last_allocated_block, threads, &P);
+    ForkJoin& fj = ForkJoin::get();
+    const unsigned nt = threads ? std::min<unsigned>(threads, fj.size()) : fj.size();
     const std::vector<int> none;
-    for (size_t l = 0; l + 1 < P.start.size(); ++l) {
-        const uint64_t lo = P.start[l], cnt = P.start[l + 1] - lo;
+    for (size_t l = 0; l + 1 < P.O.level_start.size(); ++l) {
+        const uint64_t lo = P.O.level_start[l], cnt = P.O.level_start[l + 1] - lo;
         if (cnt == 0) continue;
         SplitArgs A;
         A.B.base = arena;
@@ -3030,7 +2828,7 @@ int commit_heights(uint8_t* arena, stormck_dirty_block* blocks, const CommitPlan
         A.B.n = cnt;
         A.plan_len = static_cast<uint32_t>(std::max<uint64_t>(A.B.longest(), 1));
         A.in_place = true;
-        CommitSink sink(arena, blocks, P.order.data() + lo, out);
+        CommitSink sink(arena, blocks, P.O, lo, out);
         A.sink = &sink;
         const bool split = l == 0 && !devs.empty();
         SplitResult R;
@@ -3213,17 +3011,31 @@ int split_entry(const void* base, uint64_t stride, const uint32_t* lens, uint32_
 
 extern "C" {
 
-// ---- f1: the host leg, the split and the routed commit ----------------------------------
+// ---- f1: the device, host and split legs (plan, then run) and the routed commit ----------
+// Every leg validates first and with one rule set (commit_plan.h commit_heights): an error
+// changes nothing.
+int stormck_commit_device(void* d_arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
+                          uint64_t* last_allocated_block, uint64_t* out_checksums, void* stream) {
+    static_assert(sizeof(stormck_dirty_block) == 56, "stormck_dirty_block ABI");
+    if (n == 0) return STORMCK_OK;
+    if (!d_arena || !blocks || !last_allocated_block || !out_checksums) return fail(STORMCK_EINVAL, "null argument");
+    PhaseTimer pt("commit");
+    Heights H;
+    const int rc = commit_forest(blocks, n, revision, 0, &H);  // before the device check
+    if (rc) return rc;
+    pt.mark("heights");
+    return commit_device_run(d_arena, blocks, H, revision, last_allocated_block, out_checksums, stream, pt);
+}
+
 int stormck_commit_host(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
                         uint64_t* last_allocated_block, uint64_t* out_checksums, uint32_t threads) {
     if (n == 0) return STORMCK_OK;
     if (!arena || !blocks || !last_allocated_block || !out_checksums) return fail(STORMCK_EINVAL, "null argument");
-    CommitPlan P;
-    const int rc = commit_plan(blocks, n, revision, last_allocated_block, &P);
+    Heights H;
+    const int rc = commit_forest(blocks, n, revision, threads, &H);
     if (rc) return rc;
-    ForkJoin& fj = ForkJoin::get();
-    const unsigned nt = threads ? std::min<unsigned>(threads, fj.size()) : fj.size();
-    return commit_heights(static_cast<uint8_t*>(arena), blocks, P, out_checksums, nt, {}, 0, nullptr);
+    return commit_host_run(static_cast<uint8_t*>(arena), blocks, H, revision, last_allocated_block, out_checksums, threads,
+                           {}, 0, nullptr);
 }
 
 int stormck_commit_split(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
@@ -3240,12 +3052,11 @@ int stormck_commit_split(void* arena, stormck_dirty_block* blocks, uint64_t n, u
     const Mem mem = classify(arena, 1);
     if (mem != Mem::kMapped)
         return fail(STORMCK_EINVAL, "the split commit needs the arena registered (stormck_host_register)");
-    CommitPlan P;
-    rc = commit_plan(blocks, n, revision, last_allocated_block, &P);
+    Heights H;
+    rc = commit_forest(blocks, n, revision, host_threads, &H);
     if (rc) return rc;
-    ForkJoin& fj = ForkJoin::get();
-    const unsigned nt = host_threads ? std::min<unsigned>(host_threads, fj.size()) : fj.size();
-    return commit_heights(static_cast<uint8_t*>(arena), blocks, P, out_checksums, nt, devs, device_leaves, device_done);
+    return commit_host_run(static_cast<uint8_t*>(arena), blocks, H, revision, last_allocated_block, out_checksums,
+                           host_threads, devs, device_leaves, device_done);
 }
 
 int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_t revision,
@@ -3284,20 +3095,24 @@ int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_
     std::vector<int> devs;
     rc = route_devices(&devs);
     if (rc) return rc;
+    // one walk of the forest serves the router and the chosen leg; on the pool, as the
+    // device leg's always was (host_threads bounds the hashing, which comes after the choice)
+    Heights H;
+    rc = commit_forest(blocks, n, revision, 0, &H);
+    if (rc) return rc;
     CommitShape shape;
-    const bool planned = commit_shape(blocks, n, &shape);  // false: malformed (the host leg says why)
+    commit_shape(H, blocks, n, &shape);
     auto plan_for = [&](unsigned t) {
         return plan_commit(rt, shape, registered, t, static_cast<unsigned>(devs.size()));
     };
-    const unsigned nt = planned ? routed_threads(host_threads, [&](unsigned t) { return plan_for(t).best(); })
-                                : routed_threads(host_threads, [](unsigned) { return 0.0; });
-    LegPlan p;  // host unless the arena is registered and the forest well formed
-    if (planned) p = plan_for(nt);
+    const unsigned nt = routed_threads(host_threads, [&](unsigned t) { return plan_for(t).best(); });
+    const LegPlan p = plan_for(nt);
     if (leg_used) *leg_used = p.leg;
     if (p.leg == STORMCK_LEG_DEVICE) {
         void* d_arena = nullptr;  // the kernels read and write the registered arena in place
         HIP_TRY(hipHostGetDevicePointer(&d_arena, arena, 0));
-        return stormck_commit_device(d_arena, blocks, n, revision, last_allocated_block, out_checksums, stream);
+        PhaseTimer pt("commit");  // the heights are walked already
+        return commit_device_run(d_arena, blocks, H, revision, last_allocated_block, out_checksums, stream, pt);
     }
     // host threads read the arena now: device work the caller queued on `stream` (e.g. a
     // kernel writing blocks into the registered arena) must have landed first
@@ -3305,14 +3120,8 @@ int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_
         rc = stream_drained(static_cast<hipStream_t>(stream));
         if (rc) return rc;
     }
-    if (p.leg == STORMCK_LEG_SPLIT) {
-        CommitPlan P;
-        rc = commit_plan(blocks, n, revision, last_allocated_block, &P);
-        if (rc) return rc;
-        return commit_heights(static_cast<uint8_t*>(arena), blocks, P, out_checksums, nt, devs, STORMCK_SPLIT_BALANCED,
-                              nullptr);
-    }
-    return stormck_commit_host(arena, blocks, n, revision, last_allocated_block, out_checksums, nt);
+    return commit_host_run(static_cast<uint8_t*>(arena), blocks, H, revision, last_allocated_block, out_checksums, nt,
+                           p.leg == STORMCK_LEG_SPLIT ? devs : std::vector<int>{}, STORMCK_SPLIT_BALANCED, nullptr);
 }
 
 // ---- host-memory batches ---------------------------------------------------------------
@@ -3422,9 +3231,12 @@ int stormck_route_plan_commit(const stormck_dirty_block* blocks, uint64_t n, uin
     if (!leg) return fail(STORMCK_EINVAL, "leg is null");
     if (memory > STORMCK_MEM_PINNED) return fail(STORMCK_EINVAL, "unknown memory kind");
     if (n > 0 && !blocks) return fail(STORMCK_EINVAL, "blocks is null");
-    CommitShape shape;
-    if (!commit_shape(blocks, n, &shape)) return fail(STORMCK_EINVAL, "malformed forest (parent range or cycle)");
     const unsigned nt = host_threads ? std::min<unsigned>(host_threads, ForkJoin::get().size()) : ForkJoin::get().size();
+    Heights H;
+    if (commit_heights(blocks, n, 0, plan_par(host_threads), &H) != CommitError::Ok)
+        return fail(STORMCK_EINVAL, "malformed forest (parent range or cycle)");
+    CommitShape shape;
+    commit_shape(H, blocks, n, &shape);
     const stormck_route_rates rt = RouteModel::get().now();
     double total = 0;
     for (uint64_t b : shape.bytes) total += static_cast<double>(b);

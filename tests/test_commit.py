@@ -124,6 +124,52 @@ def test_host_leg_argument_errors():
         sc.commit_host(arena, cyc, 1, last)
 
 
+RANGE, ORIGIN, CYCLE = "parent index out of range", "origin_pointer must be 8-byte aligned", "parent links form a cycle"
+# (field, index, value) defects of the 25-leaf forest (leaves 0-24, pointer blocks 25-27,
+# root 28) and the message: with two defects, that of the lower block whose check or walk
+# fails (25 blocks walk on one thread, in index order)
+DEFECTS = [
+    ([("parent", 3, 10 ** 6)], RANGE),
+    ([("parent", 3, 29)], RANGE),
+    ([("parent", 3, -2)], RANGE),
+    ([("origin_pointer", 3, 5)], ORIGIN),
+    ([("parent", 5, 5)], CYCLE),
+    ([("parent", 25, 26), ("parent", 26, 25)], CYCLE),
+    ([("parent", 28, 3)], CYCLE),
+    ([("origin_pointer", 3, 5), ("parent", 7, 10 ** 6)], ORIGIN),
+    ([("parent", 3, 10 ** 6), ("origin_pointer", 7, 5)], RANGE),
+    ([("origin_pointer", 4, 5), ("parent", 28, 0)], CYCLE),  # block 0's walk meets the cycle first
+]
+
+
+@pytest.mark.parametrize("defects,text", DEFECTS, ids=[" + ".join(f"{f}[{i}]={v}" for f, i, v in d) for d, _ in DEFECTS])
+def test_device_and_host_legs_refuse_the_same_forests_the_same_way(defects, text):
+    """One planner, one rule set: both legs return EINVAL with the same message and leave
+    the records and the allocation counter as given. The device leg validates before it
+    looks for a device (its arena here is no memory at all); the host leg never touches
+    the arena of a forest it refuses."""
+    import ctypes
+    from storm_amd import _lib
+    b, size, last = sc.pointer_forest(25, 100, 10, slot=1024, revision=1)
+    b["birth_revision"][::3] = 1  # some would relocate
+    for field, index, value in defects:
+        b[field][index] = value
+    keep = b.copy()
+    cs = np.zeros(len(b), dtype=np.uint64)
+    L = _lib.lib
+    said = []
+    for leg in ("device", "host"):
+        la = ctypes.c_uint64(last)
+        if leg == "device":
+            rc = L.stormck_commit_device(1 << 20, b.ctypes.data, len(b), 1, ctypes.byref(la), cs.ctypes.data, None)
+        else:
+            rc = L.stormck_commit_host(1 << 20, b.ctypes.data, len(b), 1, ctypes.byref(la), cs.ctypes.data, 0)
+        assert rc == _lib.EINVAL, leg
+        said.append(_lib.last_error())
+        assert la.value == last and np.array_equal(b, keep), leg
+    assert said[0] == said[1] and said[0].startswith(text), said
+
+
 # ---------------------------------------------------------------------------
 torch = pytest.importorskip("torch")
 
@@ -402,3 +448,42 @@ def test_routed_commit_legs(dev):
             assert np.array_equal(cs, want_cs), (kind, k)
             assert np.array_equal(bp["address"], ref_b["address"]) and last2 == want_last
             assert np.array_equal(got, ref_arena), (kind, k)
+
+
+@pytest.mark.gpu
+def test_every_leg_commits_one_forest_alike(dev):
+    """One shuffled forest (1,500 leaves under fan-out 10, a third relocating) on a
+    registered host arena, through each leg in turn: the device leg in place, the host leg,
+    and the split with none, half and all of the leaves on the device. Every run leaves the
+    same records, checksums, arena and allocation counter: the oracle's serial commit."""
+    from storm_amd import blocks
+    rng = np.random.default_rng(1500)
+    n0, slot = 1500, 1024
+    b, size, last = sc.pointer_forest(n0, rng.choice([72, 256, 536, 728, 1000, 1024], size=n0), 10, slot=slot,
+                                      revision=9, first_address=100)
+    b["birth_revision"][::3] = 4
+    arena0 = np.zeros(size, dtype=np.uint8)
+    arena0[slot:slot + n0 * slot] = rng.integers(0, 256, size=n0 * slot, dtype=np.uint8)
+    bp0 = arrange(b, "shuffled", rng)
+    ref_arena, ref_b = arena0.copy(), bp0.copy()
+    want_cs, want_last = o.commit(ref_arena, ref_b, 9, last)
+    raw = np.zeros(size + 8192, dtype=np.uint8)
+    off = (-raw.ctypes.data) % 4096
+    host = raw[off:off + size]
+    blocks.RegisterHostMemory(host)
+    try:
+        for leg in ("device", "host", 0, n0 // 2, n0):
+            host[:] = arena0
+            bp = bp0.copy()
+            if leg == "device":
+                cs, last2 = sc.commit_device(blocks.HostDevicePointer(host), bp, 9, last)
+            elif leg == "host":
+                cs, last2 = sc.commit_host(host, bp, 9, last)
+            else:
+                cs, last2, done = sc.commit_split(host, bp, 9, last, device_leaves=leg)
+                assert done == leg
+            assert np.array_equal(cs, want_cs), leg
+            assert np.array_equal(bp, ref_b) and last2 == want_last, leg
+            assert np.array_equal(host, ref_arena), leg
+    finally:
+        blocks.UnregisterHostMemory(host)
