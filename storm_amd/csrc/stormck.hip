@@ -187,6 +187,12 @@ class ForkJoin {
     const std::function<void(unsigned)>* job_ = nullptr;
 };
 
+// Host threads a call may use: `threads` of the pool (0 = the pool).
+unsigned pool_threads(uint32_t threads) {
+    const unsigned size = ForkJoin::get().size();
+    return threads ? std::min<unsigned>(threads, size) : size;
+}
+
 int fail(int code, const std::string& msg) {
     g_last_error = msg;
     return code;
@@ -847,123 +853,318 @@ void par_copy(uint8_t* dst, const uint8_t* src, uint64_t bytes, uint64_t min_per
     });
 }
 
-// Host pipeline shared by checksum_host / verify_host. Blocks are processed in
-// chunks of whole blocks (<= kChunkBytes of stride); stage k's H2D+kernel+D2H run
-// on its own stream while the host fills the other stage.
-int host_pipeline(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
-                  uint64_t* out, const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad) {
+// n host blocks: block i at base + (offs ? offs[i] : i * stride), (lens ? lens[i] : len) bytes.
+struct Blocks {
+    const uint8_t* base = nullptr;
+    uint64_t stride = 0;
+    const uint64_t* offs = nullptr;
+    const uint32_t* lens = nullptr;
+    uint32_t len = 0;
+    uint64_t n = 0;
+    const uint8_t* at(uint64_t i) const { return base + (offs ? offs[i] : i * stride); }
+    uint64_t len_of(uint64_t i) const { return lens ? lens[i] : len; }
+    uint64_t bytes(uint64_t a, uint64_t b) const {
+        if (!lens) return (b - a) * len;
+        uint64_t s = 0;
+        for (uint64_t i = a; i < b; ++i) s += lens[i];
+        return s;
+    }
+    uint64_t longest() const {
+        if (!lens) return len;
+        uint64_t m = 0;
+        for (uint64_t i = 0; i < n; ++i) m = std::max<uint64_t>(m, lens[i]);
+        return m;
+    }
+};
+
+// Where a call's checksums go: called from host threads and device workers at once, on
+// disjoint blocks.
+struct Sink {
+    virtual ~Sink() = default;
+    virtual void one(uint64_t i, uint64_t h) = 0;
+    virtual void range(uint64_t i0, uint64_t cnt, const uint64_t* cs) {
+        for (uint64_t k = 0; k < cnt; ++k) one(i0 + k, cs[k]);
+    }
+};
+
+struct OutSink final : Sink {
+    uint64_t* out;
+    explicit OutSink(uint64_t* o) : out(o) {}
+    void one(uint64_t i, uint64_t h) override { out[i] = h; }
+    void range(uint64_t i0, uint64_t cnt, const uint64_t* cs) override { std::memcpy(out + i0, cs, cnt * 8); }
+};
+
+// ---- the stage engine: one chunk of host blocks through one stage ------------------------
+// The host pipeline (fixed chunks, front to back) and a split's device part (chunks claimed
+// from the back of its queue) both run their chunks through the device context's stages
+// with these three functions: issue() enqueues a chunk on the stage's stream, drain() waits
+// for it and hands its results on, abandon() clears the stages after a failure.
+
+// Where a chunk's rows are when its kernel runs.
+enum class Rows {
+    kDma,      // copied into the stage's HBM from where they are (page-locked memory)
+    kStaged,   // copied there through the stage's pinned buffer (pageable memory)
+    kStrided,  // read in place over the link, stride apart (mapped memory)
+    kGather,   // read in place at the blocks' offsets (mapped memory: a commit's height)
+};
+
+struct Chunk {
+    const Blocks* B = nullptr;
+    uint64_t first = 0, count = 0;       // blocks [first, first + count) of B
+    uint32_t plan_len = 0;               // the length the kernels plan with (HostBatch::plan_len)
+    const uint64_t* expected = nullptr;  // verify: compare instead of returning checksums
+    Rows rows = Rows::kDma;
+    const uint8_t* d_base = nullptr;     // in place: the device's address of B->base
+};
+
+// How drain() waits for a stage. The pipeline's caller spins on `done`. A split's device
+// worker waits for `ready` in the kernel (a blocking-sync event: an interrupt wakes it),
+// holding no CPU: the host threads it runs beside use all the CPU the process gets (a GPU
+// box caps it by quota, so a spinning waiter would throttle them).
+enum class Wait { kSpin, kBlock };
+
+struct StageEngine {
+    DeviceCtx* c;
+    Wait wait;
+
+    hipEvent_t event(const Stage& s) const { return wait == Wait::kSpin ? s.done : s.ready; }
+
+    // Upload the chunk's rows (or, in place, its offsets) and lengths, launch, copy the
+    // checksums (verify: the {first_bad, n_bad} pair) back into the stage's pinned buffers.
+    int issue(Stage& s, const Chunk& ch) const {
+        const Blocks& B = *ch.B;
+        const uint64_t a = ch.first, cnt = ch.count;
+        const bool in_place = ch.rows == Rows::kStrided || ch.rows == Rows::kGather;
+        const uint8_t* base = s.d_data;
+        uint64_t stride = B.stride;
+        const uint64_t* offs = nullptr;
+        if (!in_place) {
+            // bytes to move: up to the end of the last block in the chunk
+            const uint64_t bytes = (cnt - 1) * B.stride + B.len_of(a + cnt - 1);
+            const uint8_t* src = B.at(a);
+            if (ch.rows == Rows::kStaged) {
+                // the pinned buffer may be refilled only after its H2D finished: the drain of
+                // this stage before the issue guarantees that
+                par_copy(s.pinned, src, bytes);
+                src = s.pinned;
+            }
+            HIP_TRY(hipMemcpyAsync(s.d_data, src, bytes, hipMemcpyHostToDevice, s.stream));
+            if (B.lens) HIP_TRY(hipMemcpyAsync(s.d_lens, B.lens + a, cnt * 4, hipMemcpyHostToDevice, s.stream));
+        } else {
+            uint8_t* pin = s.pinned;
+            if (ch.rows == Rows::kGather) {  // the chunk's offsets
+                std::memcpy(pin, B.offs + a, cnt * 8);
+                HIP_TRY(hipMemcpyAsync(s.d_offs, pin, cnt * 8, hipMemcpyHostToDevice, s.stream));
+                pin += cnt * 8;
+                base = ch.d_base;
+                stride = 0;
+                offs = s.d_offs;
+            } else {  // strided rows, read where they are
+                base = ch.d_base + a * B.stride;
+            }
+            if (B.lens) {
+                std::memcpy(pin, B.lens + a, cnt * 4);
+                HIP_TRY(hipMemcpyAsync(s.d_lens, pin, cnt * 4, hipMemcpyHostToDevice, s.stream));
+            }
+        }
+        using ull = unsigned long long;
+        uint64_t* out = s.d_out;
+        ull *first_bad = nullptr, *n_bad = nullptr;
+        if (ch.expected) {
+            HIP_TRY(hipMemcpyAsync(s.d_expected, ch.expected + a, cnt * 8, hipMemcpyHostToDevice, s.stream));
+            s.h_result[0] = cnt;  // "no mismatch" until a block lowers it
+            s.h_result[1] = 0;
+            HIP_TRY(hipMemcpyAsync(s.d_result, s.h_result, 16, hipMemcpyHostToDevice, s.stream));
+            out = nullptr;
+            first_bad = reinterpret_cast<ull*>(s.d_result);
+            n_bad = reinterpret_cast<ull*>(s.d_result + 1);
+        }
+        const int rc = launch_checksum(base, stride, B.lens ? s.d_lens : nullptr, ch.plan_len, offs, cnt, out,
+                                       ch.expected ? s.d_expected : nullptr, first_bad, n_bad, s.stream, in_place);
+        if (rc) return rc;
+        if (ch.expected) HIP_TRY(hipMemcpyAsync(s.h_result, s.d_result, 16, hipMemcpyDeviceToHost, s.stream));
+        else HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, cnt * 8, hipMemcpyDeviceToHost, s.stream));
+        HIP_TRY(hipEventRecord(event(s), s.stream));
+        s.first = a;
+        s.count = cnt;
+        s.busy = true;
+        return STORMCK_OK;
+    }
+
+    // Wait for what the stage holds, if anything: its checksums go to `sink`, a verify's
+    // mismatches into *first_bad (the lowest index, of the call's blocks) and *n_bad.
+    int drain(Stage& s, bool verify, Sink* sink, uint64_t* first_bad, uint64_t* n_bad) const {
+        if (!s.busy) return STORMCK_OK;
+        const hipError_t e = hipEventSynchronize(event(s));
+        s.busy = false;
+        if (e != hipSuccess) return fail(STORMCK_EHIP, std::string("host stage: ") + hipGetErrorString(e));
+        // a stalled ring kernel wrote no checksum (or no mismatch) for some blocks: nothing
+        // of this stage reaches the caller
+        const int frc = take_fault(c->device, s.stream);
+        if (frc) return frc;
+        if (!verify) {
+            sink->range(s.first, s.count, s.h_out);
+        } else if (s.h_result[1] > 0) {
+            *n_bad += s.h_result[1];
+            *first_bad = std::min<uint64_t>(*first_bad, s.first + s.h_result[0]);
+        }
+        return STORMCK_OK;
+    }
+
+    // A call that fails part-way must leave nothing in flight and no stage marked busy: the
+    // stages are reused, and the next call's drain would hand that call the stale results.
+    void abandon() const {
+        for (Stage& s : c->st) {
+            (void)hipStreamSynchronize(s.stream);
+            s.busy = false;
+        }
+    }
+};
+
+// ---- one validated description of a host-memory batch --------------------------------------
+struct HostBatch {
+    Blocks B;
+    uint64_t bytes = 0;     // hashed in all
+    uint64_t longest = 0;   // the longest block
+    uint64_t extent = 0;    // from base to the end of the last block
+    uint64_t step = 8;      // a block's share of a staging chunk: the stride (one block: its length), at least 8
+    uint32_t plan_len = 0;  // what the kernels plan with: len, or the longest of per-block lengths (at least 1)
+};
+
+constexpr const char* kBlocksOverlap = "stride smaller than a block length (blocks overlap)";
+
+// The one pass over `lens`: sizes, the overlap rule, and what the legs derive from them.
+int measure_batch(uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, HostBatch* hb) {
+    *hb = HostBatch();
+    Blocks& B = hb->B;
+    B.stride = stride;
+    B.lens = lens;
+    B.len = len;
+    B.n = n;
+    hb->bytes = uint64_t{len} * n;
+    hb->longest = len;
+    if (lens) {
+        hb->bytes = hb->longest = 0;
+        for (uint64_t i = 0; i < n; ++i) {
+            hb->bytes += lens[i];
+            hb->longest = std::max<uint64_t>(hb->longest, lens[i]);
+        }
+    }
+    if (n > 1 && stride < hb->longest) return fail(STORMCK_EINVAL, kBlocksOverlap);
+    if (n == 0) return STORMCK_OK;
+    hb->extent = (n - 1) * stride + B.len_of(n - 1);
+    hb->step = n == 1 ? std::max<uint64_t>(hb->longest, 8) : std::max<uint64_t>(stride, 8);
+    hb->plan_len = lens ? static_cast<uint32_t>(std::max<uint64_t>(hb->longest, 1)) : len;
+    return STORMCK_OK;
+}
+
+// A batch entry point's arguments, checked in one order for every leg: base, the result
+// array (out or expected; result_null is the entry point's message for it), overlap, and for
+// the legs that stage whole blocks through 256 MiB chunks (staged) the block step. An empty
+// batch has nothing to check: hb->B.n == 0, and the caller zeroes its outputs.
+int host_batch(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, const void* result,
+               const char* result_null, bool staged, HostBatch* hb) {
     if (n == 0) {
-        if (first_bad) *first_bad = 0;
-        if (n_bad) *n_bad = 0;
+        *hb = HostBatch();
         return STORMCK_OK;
     }
     if (!base) return fail(STORMCK_EINVAL, "base is null");
-    if (!expected && !out) return fail(STORMCK_EINVAL, "out is null");
-    // Per-block extent actually read: max length (stride may be 0 only for n == 1).
-    uint64_t maxlen = len;
-    if (lens) {
-        maxlen = 0;
-        for (uint64_t i = 0; i < n; ++i) maxlen = std::max<uint64_t>(maxlen, lens[i]);
-    }
-    if (n > 1 && stride < maxlen) return fail(STORMCK_EINVAL, "stride smaller than a block length (blocks overlap)");
-    // with per-block lengths, the longest one is the kernels' planning length (0: none)
-    const uint32_t plan = static_cast<uint32_t>(std::max<uint64_t>(maxlen, 1));
-    const uint64_t step = n == 1 ? std::max<uint64_t>(maxlen, 8) : std::max<uint64_t>(stride, 8);
-    if (step > kChunkBytes) return fail(STORMCK_EINVAL, "block stride exceeds the staging chunk (256 MiB)");
-    const uint64_t per_chunk = std::max<uint64_t>(1, kChunkBytes / step);
+    if (!result) return fail(STORMCK_EINVAL, result_null);
+    const int rc = measure_batch(stride, lens, len, n, hb);
+    if (rc) return rc;
+    hb->B.base = static_cast<const uint8_t*>(base);
+    if (staged && hb->step > kChunkBytes) return fail(STORMCK_EINVAL, "block stride exceeds the staging chunk (256 MiB)");
+    return STORMCK_OK;
+}
 
+// An empty batch verifies: nothing mismatches.
+int empty_batch(uint64_t* first_bad, uint64_t* n_bad) {
+    if (first_bad) *first_bad = 0;
+    if (n_bad) *n_bad = 0;
+    return STORMCK_OK;
+}
+
+// The status of a verify entry point whose leg ran: mismatches are its own status.
+int verify_status(int rc, const uint64_t* n_bad) {
+    if (rc) return rc;
+    return *n_bad > 0 ? fail(STORMCK_EMISMATCH, "checksum mismatch") : STORMCK_OK;
+}
+
+// The host pipeline of checksum_host / verify_host on the current device. Blocks are
+// processed in chunks of whole blocks (<= kChunkBytes of stride); stage k's H2D+kernel+D2H
+// run on its own stream while the host fills the other stage. known: what the caller's
+// classify() said of the blocks' memory (null: not asked yet).
+int host_pipeline(const HostBatch& hb, const Mem* known, uint64_t* out, const uint64_t* expected, uint64_t* first_bad,
+                  uint64_t* n_bad) {
+    const Blocks& B = hb.B;
+    if (B.n == 0) return empty_batch(first_bad, n_bad);
     DeviceCtx* c = nullptr;
     int rc = get_ctx(&c);
     if (rc) return rc;
     std::lock_guard<std::mutex> g(c->mu);
     rc = ensure_ready(c);
     if (rc) return rc;
-
-    const Mem mem = classify(base, (n - 1) * stride + (lens ? lens[n - 1] : len));
+    const Mem mem = known ? *known : classify(B.base, hb.extent);
     if (mem == Mem::kDevice || mem == Mem::kUnreadable) return not_host_memory(mem);
-    const bool direct = mem != Mem::kPageable;
-    const uint8_t* src = static_cast<const uint8_t*>(base);
-    uint64_t fb = n, nb = 0;
 
-    auto drain = [&](Stage& s) -> int {
-        if (!s.busy) return STORMCK_OK;
-        HIP_TRY(hipEventSynchronize(s.done));
-        s.busy = false;
-        // a stalled ring kernel wrote no checksum (or no mismatch) for some blocks:
-        // nothing of this stage reaches the caller
-        const int frc = take_fault(c->device, s.stream);
-        if (frc) return frc;
-        if (expected) {
-            if (s.h_result[1] > 0) {
-                nb += s.h_result[1];
-                fb = std::min<uint64_t>(fb, s.first + s.h_result[0]);
-            }
-        } else {
-            std::memcpy(out + s.first, s.h_out, s.count * 8);
-        }
-        return STORMCK_OK;
-    };
-
-    // A call that fails part-way must not leave stages marked busy: the next call's
-    // drain would copy their stale results into that call's output.
-    auto pipeline = [&]() -> int {
-        int rc = STORMCK_OK;
-        uint64_t chunk_idx = 0;
-        for (uint64_t first = 0; first < n; first += per_chunk, ++chunk_idx) {
-            Stage& s = c->st[chunk_idx % kStages];
-            rc = drain(s);
-            if (rc) return rc;
-            const uint64_t cnt = std::min<uint64_t>(per_chunk, n - first);
-            // bytes to move: up to the end of the last block in the chunk
-            const uint64_t last_len = lens ? lens[first + cnt - 1] : len;
-            const uint64_t bytes = (cnt - 1) * stride + last_len;
-            const uint8_t* chunk_src = src + first * stride;
-            if (direct) {
-                HIP_TRY(hipMemcpyAsync(s.d_data, chunk_src, bytes, hipMemcpyHostToDevice, s.stream));
-            } else {
-                par_copy(s.pinned, chunk_src, bytes);
-                HIP_TRY(hipMemcpyAsync(s.d_data, s.pinned, bytes, hipMemcpyHostToDevice, s.stream));
-            }
-            if (lens) HIP_TRY(hipMemcpyAsync(s.d_lens, lens + first, cnt * 4, hipMemcpyHostToDevice, s.stream));
-            if (expected) {
-                HIP_TRY(hipMemcpyAsync(s.d_expected, expected + first, cnt * 8, hipMemcpyHostToDevice, s.stream));
-                const uint64_t init[2] = {cnt, 0};
-                std::memcpy(s.h_result, init, 16);
-                HIP_TRY(hipMemcpyAsync(s.d_result, s.h_result, 16, hipMemcpyHostToDevice, s.stream));
-                rc = launch_checksum(s.d_data, stride, lens ? s.d_lens : nullptr, lens ? plan : len, nullptr, cnt, nullptr,
-                                     s.d_expected, reinterpret_cast<unsigned long long*>(s.d_result),
-                                     reinterpret_cast<unsigned long long*>(s.d_result + 1), s.stream);
-                if (rc) return rc;
-                HIP_TRY(hipMemcpyAsync(s.h_result, s.d_result, 16, hipMemcpyDeviceToHost, s.stream));
-            } else {
-                rc = launch_checksum(s.d_data, stride, lens ? s.d_lens : nullptr, lens ? plan : len, nullptr, cnt, s.d_out,
-                                     nullptr, nullptr, nullptr, s.stream);
-                if (rc) return rc;
-                HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, cnt * 8, hipMemcpyDeviceToHost, s.stream));
-            }
-            HIP_TRY(hipEventRecord(s.done, s.stream));
-            s.first = first;
-            s.count = cnt;
-            s.busy = true;
-            // a pinned staging buffer may be refilled only after its H2D finished; with two
-            // stages the drain at the top of the next-but-one iteration guarantees that.
-        }
-        for (Stage& s : c->st) {
-            rc = drain(s);
-            if (rc) return rc;
-        }
-        return STORMCK_OK;
-    };
-    rc = pipeline();
+    const StageEngine eng{c, Wait::kSpin};
+    OutSink sink(out);
+    Chunk ch;
+    ch.B = &B;
+    ch.plan_len = hb.plan_len;
+    ch.expected = expected;
+    ch.rows = mem == Mem::kPageable ? Rows::kStaged : Rows::kDma;
+    const uint64_t per_chunk = std::max<uint64_t>(1, kChunkBytes / hb.step);
+    uint64_t fb = B.n, nb = 0;
+    for (uint64_t k = 0; ch.first < B.n && rc == STORMCK_OK; ch.first += per_chunk, ++k) {
+        Stage& s = c->st[k % kStages];
+        rc = eng.drain(s, expected != nullptr, &sink, &fb, &nb);
+        ch.count = std::min<uint64_t>(per_chunk, B.n - ch.first);
+        if (rc == STORMCK_OK) rc = eng.issue(s, ch);
+    }
+    for (Stage& s : c->st)
+        if (rc == STORMCK_OK) rc = eng.drain(s, expected != nullptr, &sink, &fb, &nb);
     if (rc) {
-        for (Stage& s : c->st) {
-            if (s.busy) (void)hipStreamSynchronize(s.stream);
-            s.busy = false;
-        }
+        eng.abandon();
         return rc;
     }
     if (first_bad) *first_bad = fb;
     if (n_bad) *n_bad = nb;
+    return STORMCK_OK;
+}
+
+// The same from raw arguments (out or expected is set): validate, then run.
+int host_pipeline(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, uint64_t* out,
+                  const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad) {
+    HostBatch hb;
+    const int rc = host_batch(base, stride, lens, len, n, expected ? static_cast<const void*>(expected) : out,
+                              "out is null", true, &hb);
+    return rc ? rc : host_pipeline(hb, nullptr, out, expected, first_bad, n_bad);
+}
+
+// A caller's device list: 1..64 entries.
+int check_device_list(const int* devices, int n_devices) {
+    if (!devices || n_devices <= 0 || n_devices > 64) return fail(STORMCK_EINVAL, "devices: 1..64 entries");
+    return STORMCK_OK;
+}
+
+// Visible gfx950 devices, in the order given; unique: each once.
+int check_devices(const int* devices, int n_devices, bool unique, std::vector<int>* out) {
+    int rc = check_device_list(devices, n_devices);
+    if (rc) return rc;
+    int count = 0;
+    HIP_TRY(hipGetDeviceCount(&count));
+    out->clear();
+    for (int k = 0; k < n_devices; ++k) {
+        if (devices[k] < 0 || devices[k] >= count)
+            return fail(STORMCK_EINVAL, "devices[" + std::to_string(k) + "] = " + std::to_string(devices[k]) +
+                                            " is not a visible device");
+        hipDeviceProp_t prop;
+        HIP_TRY(hipGetDeviceProperties(&prop, devices[k]));
+        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+            return fail(STORMCK_ENODEV, "devices[" + std::to_string(k) + "] is not gfx950: " + prop.gcnArchName);
+        if (!unique || std::find(out->begin(), out->end(), devices[k]) == out->end()) out->push_back(devices[k]);
+    }
     return STORMCK_OK;
 }
 
@@ -977,25 +1178,14 @@ int host_pipeline(const void* base, uint64_t stride, const uint32_t* lens, uint3
 int host_pipeline_multi(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
                         uint64_t* out, const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad,
                         const int* devices, int n_devices) {
-    if (!devices || n_devices <= 0 || n_devices > 64) return fail(STORMCK_EINVAL, "devices: 1..64 entries");
-    if (n == 0) {
-        if (first_bad) *first_bad = 0;
-        if (n_bad) *n_bad = 0;
-        return STORMCK_OK;
-    }
-    int rc = device_check();
+    int rc = check_device_list(devices, n_devices);
     if (rc) return rc;
-    int count = 0;
-    HIP_TRY(hipGetDeviceCount(&count));
-    for (int k = 0; k < n_devices; ++k) {
-        if (devices[k] < 0 || devices[k] >= count)
-            return fail(STORMCK_EINVAL, "devices[" + std::to_string(k) + "] = " + std::to_string(devices[k]) +
-                                            " is not a visible device");
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, devices[k]));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(STORMCK_ENODEV, "devices[" + std::to_string(k) + "] is not gfx950: " + prop.gcnArchName);
-    }
+    if (n == 0) return empty_batch(first_bad, n_bad);
+    rc = device_check();
+    if (rc) return rc;
+    std::vector<int> listed;  // duplicates kept: a device listed twice gets two ranges
+    rc = check_devices(devices, n_devices, false, &listed);
+    if (rc) return rc;
     const uint64_t parts = std::min<uint64_t>(static_cast<uint64_t>(n_devices), std::max<uint64_t>(n, 1));
     if (parts == 1 || n <= 1) {
         int prev = 0;
@@ -1245,13 +1435,7 @@ int stormck_checksum_host(const void* base, uint64_t stride, const uint32_t* len
 int stormck_verify_host(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
                         const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad) {
     if (!expected || !first_bad || !n_bad) return fail(STORMCK_EINVAL, "null argument");
-    int rc = host_pipeline(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad);
-    if (rc) return rc;
-    if (*n_bad > 0) {
-        g_last_error = "checksum mismatch";
-        return STORMCK_EMISMATCH;
-    }
-    return STORMCK_OK;
+    return verify_status(host_pipeline(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad), n_bad);
 }
 
 int stormck_checksum_host_multi(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
@@ -1264,13 +1448,8 @@ int stormck_verify_host_multi(const void* base, uint64_t stride, const uint32_t*
                               const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, const int* devices,
                               int n_devices) {
     if (!expected || !first_bad || !n_bad) return fail(STORMCK_EINVAL, "null argument");
-    int rc = host_pipeline_multi(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, devices, n_devices);
-    if (rc) return rc;
-    if (*n_bad > 0) {
-        g_last_error = "checksum mismatch";
-        return STORMCK_EMISMATCH;
-    }
-    return STORMCK_OK;
+    return verify_status(
+        host_pipeline_multi(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, devices, n_devices), n_bad);
 }
 
 uint64_t stormck_xxh64(const void* p, uint64_t n_bytes) {
@@ -1641,12 +1820,7 @@ int stormck_read_verify_fd(int fd, const uint64_t* addresses, const uint32_t* le
                                                  : std::string("short read (block beyond end of device)");
         return fail(STORMCK_EINVAL, what + " at block index " + std::to_string(bad_index.load()));
     }
-    if (rc) return rc;
-    if (*n_bad > 0) {
-        g_last_error = "checksum mismatch";
-        return STORMCK_EMISMATCH;
-    }
-    return STORMCK_OK;
+    return verify_status(rc, n_bad);
 }
 
 int stormck_key_tags_device(const void* d_keys, uint64_t stride, const uint64_t* d_offsets, const uint32_t* d_lens,
@@ -2084,23 +2258,9 @@ int route_devices(std::vector<int>* out) {
     return STORMCK_OK;
 }
 
-// Visible gfx950 devices, each once, in the order given.
-int check_devices(const int* devices, int n_devices, std::vector<int>* out) {
-    if (!devices || n_devices <= 0 || n_devices > 64) return fail(STORMCK_EINVAL, "devices: 1..64 entries");
-    int count = 0;
-    HIP_TRY(hipGetDeviceCount(&count));
-    out->clear();
-    for (int k = 0; k < n_devices; ++k) {
-        if (devices[k] < 0 || devices[k] >= count)
-            return fail(STORMCK_EINVAL, "devices[" + std::to_string(k) + "] = " + std::to_string(devices[k]) +
-                                            " is not a visible device");
-        hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, devices[k]));
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return fail(STORMCK_ENODEV, "devices[" + std::to_string(k) + "] is not gfx950: " + prop.gcnArchName);
-        if (std::find(out->begin(), out->end(), devices[k]) == out->end()) out->push_back(devices[k]);
-    }
-    return STORMCK_OK;
+// The devices a split may use: the caller's list, each device once, or the route devices.
+int split_devices(const int* devices, int n_devices, std::vector<int>* out) {
+    return (devices || n_devices) ? check_devices(devices, n_devices, true, out) : route_devices(out);
 }
 
 // Threads the host part of a routed call may use: host_threads (0 = the pool). While another
@@ -2110,10 +2270,9 @@ int check_devices(const int* devices, int n_devices, std::vector<int>* out) {
 // predicted time with t threads.
 template <class TimeWith>
 unsigned routed_threads(uint32_t host_threads, TimeWith&& time_with) {
-    ForkJoin& fj = ForkJoin::get();
-    const unsigned nt = host_threads ? std::min<unsigned>(host_threads, fj.size()) : fj.size();
+    const unsigned nt = pool_threads(host_threads);
     if (nt <= 1) return 1;
-    const double busy = fj.busy_for_us();
+    const double busy = ForkJoin::get().busy_for_us();
     if (busy <= 0) return nt;
     return busy + time_with(nt) < time_with(1) ? nt : 1;
 }
@@ -2192,30 +2351,6 @@ class DevWorker {
     bool pending_ = false;
 };
 
-// n host blocks: block i at base + (offs ? offs[i] : i * stride), (lens ? lens[i] : len) bytes.
-struct Blocks {
-    const uint8_t* base = nullptr;
-    uint64_t stride = 0;
-    const uint64_t* offs = nullptr;
-    const uint32_t* lens = nullptr;
-    uint32_t len = 0;
-    uint64_t n = 0;
-    const uint8_t* at(uint64_t i) const { return base + (offs ? offs[i] : i * stride); }
-    uint64_t len_of(uint64_t i) const { return lens ? lens[i] : len; }
-    uint64_t bytes(uint64_t a, uint64_t b) const {
-        if (!lens) return (b - a) * len;
-        uint64_t s = 0;
-        for (uint64_t i = a; i < b; ++i) s += lens[i];
-        return s;
-    }
-    uint64_t longest() const {
-        if (!lens) return len;
-        uint64_t m = 0;
-        for (uint64_t i = 0; i < n; ++i) m = std::max<uint64_t>(m, lens[i]);
-        return m;
-    }
-};
-
 // XXH64 of blocks [a, b), four chains at once where the CPU has AVX-512: take(i, hash).
 template <class Take>
 void hash_blocks(const Blocks& B, uint64_t a, uint64_t b, Take&& take) {
@@ -2233,23 +2368,6 @@ void hash_blocks(const Blocks& B, uint64_t a, uint64_t b, Take&& take) {
     }
     for (; i < b; ++i) take(i, host::xxh64(B.at(i), B.len_of(i)));
 }
-
-// Where a call's checksums go: called from host threads and device workers at once, on
-// disjoint blocks.
-struct Sink {
-    virtual ~Sink() = default;
-    virtual void one(uint64_t i, uint64_t h) = 0;
-    virtual void range(uint64_t i0, uint64_t cnt, const uint64_t* cs) {
-        for (uint64_t k = 0; k < cnt; ++k) one(i0 + k, cs[k]);
-    }
-};
-
-struct OutSink final : Sink {
-    uint64_t* out;
-    explicit OutSink(uint64_t* o) : out(o) {}
-    void one(uint64_t i, uint64_t h) override { out[i] = h; }
-    void range(uint64_t i0, uint64_t cnt, const uint64_t* cs) override { std::memcpy(out + i0, cs, cnt * 8); }
-};
 
 // The blocks of one call, shared by its host threads (from the front) and its devices
 // (from the back). Balanced: a device claims b bytes so that, with I bytes in flight and
@@ -2322,13 +2440,9 @@ struct DevRun {
     uint64_t first_bytes = 0;             // that chunk's bytes
 };
 
-// A split's device worker waits for its chunks in the kernel (a blocking-sync event: an
-// interrupt wakes it), holding no CPU: the host threads it runs beside use all the CPU the
-// process gets (a GPU box caps it by quota, so a spinning waiter would throttle them).
-hipError_t wait_event(hipEvent_t e) { return hipEventSynchronize(e); }
-
 // One device's part of a split, on its worker thread (the current device is its own):
-// chunks claimed from the back of the queue through the device context's two stages.
+// chunks claimed from the back of the queue through the device context's two stages (the
+// stage engine, waiting without spinning: Wait::kBlock), and the timing the route model learns from.
 // In-place mode (mapped memory: registered, as the Go binding's cache.data) lets the kernels
 // read the chunk's blocks over the link where they are, strided or at the offsets of a
 // commit's scattered blocks, and needs no copy engine: a chunk is one launch and one small
@@ -2374,88 +2488,27 @@ void device_part(const SplitArgs& A, SplitQueue& q, double lat_us, DevRun* r) {
                                               std::max(kSplitDmaBytes, bpb * static_cast<double>(B.n) / 16.0) / bpb)));
     double inflight = 0, t0 = 0, t_end = 0;
     double stage_bytes[kStages] = {};
-    using ull = unsigned long long;
+    const StageEngine eng{c, Wait::kBlock};
+    Chunk ch;
+    ch.B = &B;
+    ch.plan_len = B.lens ? A.plan_len : B.len;
+    ch.expected = A.expected;
+    ch.d_base = d_base;
 
     auto drain = [&](int k) -> int {
         Stage& s = c->st[k];
         if (!s.busy) return STORMCK_OK;
-        const hipError_t e = wait_event(s.ready);
-        s.busy = false;
+        const uint64_t cnt = s.count;
+        const int drc = eng.drain(s, A.expected != nullptr, A.sink, &r->first_bad, &r->n_bad);
         inflight -= stage_bytes[k];
-        if (e != hipSuccess) return fail(STORMCK_EHIP, std::string("split: ") + hipGetErrorString(e));
-        const int frc = take_fault(c->device, s.stream);  // a stalled ring kernel left blocks unhashed
-        if (frc) return frc;
-        if (A.expected) {
-            if (s.h_result[1] > 0) {
-                r->n_bad += s.h_result[1];
-                r->first_bad = std::min<uint64_t>(r->first_bad, s.first + s.h_result[0]);
-            }
-        } else {
-            A.sink->range(s.first, s.count, s.h_out);
-        }
-        r->blocks += s.count;
+        if (drc) return drc;
+        r->blocks += cnt;
         r->bytes += static_cast<uint64_t>(stage_bytes[k]);
         t_end = now_us();
         if (r->first_done == 0) {
             r->first_done = t_end;
             r->first_bytes = static_cast<uint64_t>(stage_bytes[k]);
         }
-        return STORMCK_OK;
-    };
-    auto issue = [&](int k, uint64_t a, uint64_t cnt) -> int {
-        Stage& s = c->st[k];
-        const uint8_t* base = nullptr;
-        uint64_t stride = 0;
-        const uint64_t* offs = nullptr;
-        // strided rows go through the copy engine when the chunk is large (55.7 GB/s against
-        // ~43 for kernels reading in place, profiles/r05_second/), in place when it is small
-        // (no copy to wait for: the first chunk returns sooner)
-        if (!B.offs && (!A.in_place || stage_bytes[k] >= kSplitDmaBytes)) {
-            const uint64_t bytes = (cnt - 1) * B.stride + B.len_of(a + cnt - 1);
-            HIP_TRY(hipMemcpyAsync(s.d_data, B.at(a), bytes, hipMemcpyHostToDevice, s.stream));
-            if (B.lens) HIP_TRY(hipMemcpyAsync(s.d_lens, B.lens + a, cnt * 4, hipMemcpyHostToDevice, s.stream));
-            base = s.d_data;
-            stride = B.stride;
-        } else {
-            uint8_t* pin = s.pinned;
-            if (B.offs) {  // a gather (a commit height): the chunk's offsets
-                std::memcpy(pin, B.offs + a, cnt * 8);
-                HIP_TRY(hipMemcpyAsync(s.d_offs, pin, cnt * 8, hipMemcpyHostToDevice, s.stream));
-                pin += cnt * 8;
-                base = d_base;
-                offs = s.d_offs;
-            } else {  // strided rows, read where they are
-                base = d_base + a * B.stride;
-                stride = B.stride;
-            }
-            if (B.lens) {
-                std::memcpy(pin, B.lens + a, cnt * 4);
-                HIP_TRY(hipMemcpyAsync(s.d_lens, pin, cnt * 4, hipMemcpyHostToDevice, s.stream));
-            }
-        }
-        const uint32_t* dl = B.lens ? s.d_lens : nullptr;
-        const uint32_t plan = B.lens ? A.plan_len : B.len;
-        int lrc;
-        if (A.expected) {
-            HIP_TRY(hipMemcpyAsync(s.d_expected, A.expected + a, cnt * 8, hipMemcpyHostToDevice, s.stream));
-            s.h_result[0] = cnt;
-            s.h_result[1] = 0;
-            HIP_TRY(hipMemcpyAsync(s.d_result, s.h_result, 16, hipMemcpyHostToDevice, s.stream));
-            lrc = launch_checksum(base, stride, dl, plan, offs, cnt, nullptr, s.d_expected,
-                                  reinterpret_cast<ull*>(s.d_result), reinterpret_cast<ull*>(s.d_result + 1), s.stream,
-                                  A.in_place && base != s.d_data);
-            if (lrc) return lrc;
-            HIP_TRY(hipMemcpyAsync(s.h_result, s.d_result, 16, hipMemcpyDeviceToHost, s.stream));
-        } else {
-            lrc = launch_checksum(base, stride, dl, plan, offs, cnt, s.d_out, nullptr, nullptr, nullptr, s.stream,
-                                  A.in_place && base != s.d_data);
-            if (lrc) return lrc;
-            HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out, cnt * 8, hipMemcpyDeviceToHost, s.stream));
-        }
-        HIP_TRY(hipEventRecord(s.ready, s.stream));
-        s.first = a;
-        s.count = cnt;
-        s.busy = true;
         return STORMCK_OK;
     };
 
@@ -2469,15 +2522,19 @@ void device_part(const SplitArgs& A, SplitQueue& q, double lat_us, DevRun* r) {
         if (t0 == 0) r->first_issue = t0 = now_us();
         stage_bytes[st] = static_cast<double>(B.bytes(a, b));
         inflight += stage_bytes[st];
-        rc = issue(st, a, b - a);
+        ch.first = a;
+        ch.count = b - a;
+        // strided rows go through the copy engine when the chunk is large (55.7 GB/s against
+        // ~43 for kernels reading in place, profiles/r05_second/), in place when it is small
+        // (no copy to wait for: the first chunk returns sooner)
+        ch.rows = B.offs ? Rows::kGather
+                         : (!A.in_place || stage_bytes[st] >= kSplitDmaBytes ? Rows::kDma : Rows::kStrided);
+        rc = eng.issue(c->st[st], ch);
         if (rc) break;
     }
     for (int k = 0; k < kStages && rc == STORMCK_OK; ++k) rc = drain(k);
-    if (rc) {  // nothing of this call may stay in flight: the stages are reused
-        for (Stage& s : c->st) {
-            (void)hipStreamSynchronize(s.stream);
-            s.busy = false;
-        }
+    if (rc) {
+        eng.abandon();
         return failed(rc);
     }
     r->busy_us = t_end > t0 ? t_end - t0 : 0;
@@ -2634,24 +2691,6 @@ int split_run(SplitArgs& A, const std::vector<int>& devs, unsigned pl, uint64_t 
 }
 
 // ---- the batch cost model ----------------------------------------------------------
-struct BatchShape {
-    uint64_t bytes = 0, longest = 0;
-};
-
-// Bytes hashed and the longest block; false: blocks overlap (stride below a length).
-bool batch_shape(uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, BatchShape* s) {
-    if (lens) {
-        for (uint64_t i = 0; i < n; ++i) {
-            s->bytes += lens[i];
-            s->longest = std::max<uint64_t>(s->longest, lens[i]);
-        }
-    } else {
-        s->bytes = uint64_t{len} * n;
-        s->longest = len;
-    }
-    return n <= 1 || stride >= s->longest;
-}
-
 struct LegPlan {
     uint32_t leg = STORMCK_LEG_HOST;
     double us[3] = {0, INFINITY, INFINITY};  // host, device, split
@@ -2703,7 +2742,7 @@ LegPlan host_only_plan(const stormck_route_rates& r, double bytes) {
     return p;
 }
 
-LegPlan plan_batch(const stormck_route_rates& r, uint64_t n, const BatchShape& s, bool pinned, bool staged_ok,
+LegPlan plan_batch(const stormck_route_rates& r, uint64_t n, const HostBatch& s, bool pinned, bool staged_ok,
                    unsigned nt, unsigned ndev) {
     LegPlan p;
     const unsigned pl = host_threads_for(s.bytes, nt);
@@ -2852,56 +2891,15 @@ int stream_drained(hipStream_t st) {
     return STORMCK_OK;
 }
 
-// Host arguments of the batch entry points, checked the same way for every leg.
-int batch_args(const void* base, uint64_t n, const uint64_t* out_or_expected) {
-    if (n == 0) return STORMCK_OK;
-    if (!base) return fail(STORMCK_EINVAL, "base is null");
-    if (!out_or_expected) return fail(STORMCK_EINVAL, "null argument");
-    return STORMCK_OK;
-}
-
-Blocks batch_blocks(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n) {
-    Blocks B;
-    B.base = static_cast<const uint8_t*>(base);
-    B.stride = stride;
-    B.lens = lens;
-    B.len = len;
-    B.n = n;
-    return B;
-}
-
-// The host leg of a batch on `threads` pool threads (0 = the pool): no device involved.
-// checked: the caller has already classified `base` (the routed call).
-int batch_host_leg(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, uint64_t* out,
-                   const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, uint32_t threads,
-                   bool checked = false) {
-    BatchShape s;
-    if (!batch_shape(stride, lens, len, n, &s)) return fail(STORMCK_EINVAL, "stride smaller than a block length (blocks overlap)");
-    if (!checked && !host_readable(base, (n - 1) * stride + (lens ? lens[n - 1] : len)))
-        return fail(STORMCK_EINVAL, "base is not readable host memory");
-    ForkJoin& fj = ForkJoin::get();
-    const unsigned nt = threads ? std::min<unsigned>(threads, fj.size()) : fj.size();
+// A validated batch on `pl` host threads and the devices `devs` at once (split_run): the
+// host leg when devs is empty, else the split leg (stormck_checksum_split / the routed
+// batch's split), whose devices read the blocks in place or by DMA.
+int batch_legs(const HostBatch& hb, uint64_t* out, const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad,
+               const std::vector<int>& devs, unsigned pl, uint64_t device_blocks, uint64_t* device_done, bool in_place) {
     SplitArgs A;
-    A.B = batch_blocks(base, stride, lens, len, n);
-    A.expected = expected;
-    OutSink sink(out);
-    A.sink = &sink;
-    SplitResult R;
-    const int rc = split_run(A, {}, host_threads_for(s.bytes, nt), STORMCK_SPLIT_BALANCED, &R);
-    if (rc) return rc;
-    if (first_bad) *first_bad = R.first_bad;
-    if (n_bad) *n_bad = R.n_bad;
-    return STORMCK_OK;
-}
-
-// The split leg of a batch (stormck_checksum_split / the routed batch's split).
-int batch_split_leg(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, uint64_t* out,
-                    const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, const std::vector<int>& devs,
-                    unsigned pl, uint64_t device_blocks, uint64_t* device_done, bool in_place) {
-    SplitArgs A;
-    A.B = batch_blocks(base, stride, lens, len, n);
+    A.B = hb.B;
     A.in_place = in_place;
-    A.plan_len = lens ? static_cast<uint32_t>(std::max<uint64_t>(A.B.longest(), 1)) : len;
+    A.plan_len = hb.plan_len;
     A.expected = expected;
     OutSink sink(out);
     A.sink = &sink;
@@ -2914,42 +2912,55 @@ int batch_split_leg(const void* base, uint64_t stride, const uint32_t* lens, uin
     return STORMCK_OK;
 }
 
+// The host leg of a batch on at most `nt` pool threads: no device involved.
+int batch_host_leg(const HostBatch& hb, uint64_t* out, const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad,
+                   unsigned nt) {
+    return batch_legs(hb, out, expected, first_bad, n_bad, {}, host_threads_for(hb.bytes, nt), STORMCK_SPLIT_BALANCED,
+                      nullptr, false);
+}
+
+// The explicit host-leg entry points: any readable host memory, `threads` pool threads (0 = the
+// pool). The host leg stages nothing, so it has no limit on the block step.
+int host_leg_entry(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, uint64_t* out,
+                   const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, uint32_t threads) {
+    HostBatch hb;
+    const int rc = host_batch(base, stride, lens, len, n, expected ? static_cast<const void*>(expected) : out,
+                              "null argument", false, &hb);
+    if (rc || n == 0) return rc;
+    if (!host_readable(base, hb.extent)) return fail(STORMCK_EINVAL, "base is not readable host memory");
+    return batch_host_leg(hb, out, expected, first_bad, n_bad, pool_threads(threads));
+}
+
 // The routed batch: the leg the cost model predicts is fastest (*leg_used).
 int batch_routed(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n, uint64_t* out,
                  const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, uint32_t host_threads,
                  uint32_t* leg_used) {
     if (leg_used) *leg_used = STORMCK_LEG_NONE;
-    int rc = batch_args(base, n, expected ? expected : out);
+    HostBatch hb;
+    int rc = host_batch(base, stride, lens, len, n, expected ? static_cast<const void*>(expected) : out, "null argument",
+                        false, &hb);
     if (rc) return rc;
-    BatchShape s;
-    if (!batch_shape(stride, lens, len, n, &s)) return fail(STORMCK_EINVAL, "stride smaller than a block length (blocks overlap)");
     rc = device_check();  // a batch entry point of the GPU engine: no device, no batch
     if (rc) return rc;
-    if (n == 0) {
-        if (first_bad) *first_bad = 0;
-        if (n_bad) *n_bad = 0;
-        return STORMCK_OK;
-    }
-    const uint64_t extent = (n - 1) * stride + (lens ? lens[n - 1] : len);
+    if (n == 0) return empty_batch(first_bad, n_bad);
     // a batch that one host thread hashes faster than any device can start returning takes
     // the host leg without planning (host_only); it only needs the range to be readable host
     // memory (registered, or readable: what the host leg alone checks), not its kind
-    if (host_only(RouteModel::get().host_thread(), static_cast<double>(s.bytes))) {
-        if (!in_registered(base, extent) && !host_readable(base, extent)) return not_host_memory(classify(base, extent));
+    if (host_only(RouteModel::get().host_thread(), static_cast<double>(hb.bytes))) {
+        if (!in_registered(base, hb.extent) && !host_readable(base, hb.extent))
+            return not_host_memory(classify(base, hb.extent));
         if (leg_used) *leg_used = STORMCK_LEG_HOST;
-        return batch_host_leg(base, stride, lens, len, n, out, expected, first_bad, n_bad, 1, true);
+        return batch_host_leg(hb, out, expected, first_bad, n_bad, 1);
     }
-    const Mem mem = classify(base, extent);
+    const Mem mem = classify(base, hb.extent);
     if (mem == Mem::kDevice || mem == Mem::kUnreadable) return not_host_memory(mem);
     const stormck_route_rates rt = RouteModel::get().now();
     std::vector<int> devs;
     rc = route_devices(&devs);
     if (rc) return rc;
-    // the device pipeline stages whole blocks through 256 MiB chunks
-    const uint64_t step = n == 1 ? std::max<uint64_t>(s.longest, 8) : std::max<uint64_t>(stride, 8);
     const bool pinned = mem != Mem::kPageable;
-    auto plan_for = [&](unsigned t) {
-        return plan_batch(rt, n, s, pinned, step <= kChunkBytes, t, static_cast<unsigned>(devs.size()));
+    auto plan_for = [&](unsigned t) {  // the device pipeline stages whole blocks through 256 MiB chunks
+        return plan_batch(rt, n, hb, pinned, hb.step <= kChunkBytes, t, static_cast<unsigned>(devs.size()));
     };
     const unsigned nt = routed_threads(host_threads, [&](unsigned t) { return plan_for(t).best(); });
     const LegPlan p = plan_for(nt);
@@ -2959,20 +2970,20 @@ int batch_routed(const void* base, uint64_t stride, const uint32_t* lens, uint32
         int cur = 0;
         HIP_TRY(hipGetDevice(&cur));
         rc = devs.size() == 1 && devs[0] == cur
-                 ? host_pipeline(base, stride, lens, len, n, out, expected, first_bad, n_bad)
+                 ? host_pipeline(hb, &mem, out, expected, first_bad, n_bad)
                  : host_pipeline_multi(base, stride, lens, len, n, out, expected, first_bad, n_bad, devs.data(),
                                        static_cast<int>(devs.size()));
         if (rc == STORMCK_OK)
-            RouteModel::get().learn_link(pinned ? Link::kPinned : Link::kPageable, s.bytes / devs.size(),
+            RouteModel::get().learn_link(pinned ? Link::kPinned : Link::kPageable, hb.bytes / devs.size(),
                                          now_us() - t0 - kDevBatchCallUs -
-                                             static_cast<double>(s.longest) / kDevChainBytesPerUs);
+                                             static_cast<double>(hb.longest) / kDevChainBytesPerUs);
         return rc;
     }
-    const unsigned pl = host_threads_for(s.bytes, nt);
+    const unsigned pl = host_threads_for(hb.bytes, nt);
     if (p.leg == STORMCK_LEG_SPLIT)
-        return batch_split_leg(base, stride, lens, len, n, out, expected, first_bad, n_bad, devs, pl,
-                               STORMCK_SPLIT_BALANCED, nullptr, mem == Mem::kMapped);
-    return batch_host_leg(base, stride, lens, len, n, out, expected, first_bad, n_bad, pl, true);
+        return batch_legs(hb, out, expected, first_bad, n_bad, devs, pl, STORMCK_SPLIT_BALANCED, nullptr,
+                          mem == Mem::kMapped);
+    return batch_host_leg(hb, out, expected, first_bad, n_bad, pl);
 }
 
 // The explicit split entry points: pinned or registered memory, the listed devices (or the
@@ -2981,30 +2992,22 @@ int split_entry(const void* base, uint64_t stride, const uint32_t* lens, uint32_
                 const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, const int* devices, int n_devices,
                 uint32_t host_threads, uint64_t device_blocks, uint64_t* device_done) {
     if (device_done) *device_done = 0;
-    int rc = batch_args(base, n, expected ? expected : out);
+    HostBatch hb;
+    int rc = host_batch(base, stride, lens, len, n, expected ? static_cast<const void*>(expected) : out, "null argument",
+                        true, &hb);
     if (rc) return rc;
-    BatchShape s;
-    if (!batch_shape(stride, lens, len, n, &s)) return fail(STORMCK_EINVAL, "stride smaller than a block length (blocks overlap)");
     rc = device_check();
     if (rc) return rc;
     std::vector<int> devs;
-    rc = (devices || n_devices) ? check_devices(devices, n_devices, &devs) : route_devices(&devs);
+    rc = split_devices(devices, n_devices, &devs);
     if (rc) return rc;
-    if (n == 0) {
-        if (first_bad) *first_bad = 0;
-        if (n_bad) *n_bad = 0;
-        return STORMCK_OK;
-    }
-    const Mem mem = classify(base, (n - 1) * stride + (lens ? lens[n - 1] : len));
+    if (n == 0) return empty_batch(first_bad, n_bad);
+    const Mem mem = classify(base, hb.extent);
     if (mem == Mem::kDevice || mem == Mem::kUnreadable) return not_host_memory(mem);
     if (mem == Mem::kPageable)
         return fail(STORMCK_EINVAL, "the split leg needs pinned or registered host memory (stormck_host_register)");
-    const uint64_t step = n == 1 ? std::max<uint64_t>(s.longest, 8) : std::max<uint64_t>(stride, 8);
-    if (step > kChunkBytes) return fail(STORMCK_EINVAL, "block stride exceeds the staging chunk (256 MiB)");
-    ForkJoin& fj = ForkJoin::get();
-    const unsigned nt = host_threads ? std::min<unsigned>(host_threads, fj.size()) : fj.size();
-    return batch_split_leg(base, stride, lens, len, n, out, expected, first_bad, n_bad, devs,
-                           host_threads_for(s.bytes, nt), device_blocks, device_done, mem == Mem::kMapped);
+    return batch_legs(hb, out, expected, first_bad, n_bad, devs, host_threads_for(hb.bytes, pool_threads(host_threads)),
+                      device_blocks, device_done, mem == Mem::kMapped);
 }
 
 }  // namespace
@@ -3047,7 +3050,7 @@ int stormck_commit_split(void* arena, stormck_dirty_block* blocks, uint64_t n, u
     int rc = device_check();
     if (rc) return rc;
     std::vector<int> devs;
-    rc = (devices || n_devices) ? check_devices(devices, n_devices, &devs) : route_devices(&devs);
+    rc = split_devices(devices, n_devices, &devs);
     if (rc) return rc;
     const Mem mem = classify(arena, 1);
     if (mem != Mem::kMapped)
@@ -3127,9 +3130,7 @@ int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_
 // ---- host-memory batches ---------------------------------------------------------------
 int stormck_checksum_host_leg(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
                               uint64_t* out, uint32_t threads) {
-    const int rc = batch_args(base, n, out);
-    if (rc || n == 0) return rc;
-    return batch_host_leg(base, stride, lens, len, n, out, nullptr, nullptr, nullptr, threads);
+    return host_leg_entry(base, stride, lens, len, n, out, nullptr, nullptr, nullptr, threads);
 }
 
 int stormck_verify_host_leg(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
@@ -3137,12 +3138,7 @@ int stormck_verify_host_leg(const void* base, uint64_t stride, const uint32_t* l
     if (!first_bad || !n_bad) return fail(STORMCK_EINVAL, "null argument");
     *first_bad = n;
     *n_bad = 0;
-    int rc = batch_args(base, n, expected);
-    if (rc || n == 0) return rc;
-    rc = batch_host_leg(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, threads);
-    if (rc) return rc;
-    if (*n_bad > 0) return fail(STORMCK_EMISMATCH, "checksum mismatch");
-    return STORMCK_OK;
+    return verify_status(host_leg_entry(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, threads), n_bad);
 }
 
 int stormck_checksum_batch(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
@@ -3155,10 +3151,8 @@ int stormck_verify_batch(const void* base, uint64_t stride, const uint32_t* lens
                          uint32_t* leg_used) {
     if (leg_used) *leg_used = STORMCK_LEG_NONE;
     if (!first_bad || !n_bad) return fail(STORMCK_EINVAL, "null argument");
-    const int rc = batch_routed(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, host_threads, leg_used);
-    if (rc) return rc;
-    if (*n_bad > 0) return fail(STORMCK_EMISMATCH, "checksum mismatch");
-    return STORMCK_OK;
+    return verify_status(
+        batch_routed(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, host_threads, leg_used), n_bad);
 }
 
 int stormck_checksum_split(const void* base, uint64_t stride, const uint32_t* lens, uint32_t len, uint64_t n,
@@ -3172,11 +3166,9 @@ int stormck_verify_split(const void* base, uint64_t stride, const uint32_t* lens
                          const uint64_t* expected, uint64_t* first_bad, uint64_t* n_bad, const int* devices,
                          int n_devices, uint32_t host_threads, uint64_t device_blocks, uint64_t* device_done) {
     if (!first_bad || !n_bad) return fail(STORMCK_EINVAL, "null argument");
-    const int rc = split_entry(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, devices, n_devices,
-                               host_threads, device_blocks, device_done);
-    if (rc) return rc;
-    if (*n_bad > 0) return fail(STORMCK_EMISMATCH, "checksum mismatch");
-    return STORMCK_OK;
+    return verify_status(split_entry(base, stride, lens, len, n, nullptr, expected, first_bad, n_bad, devices, n_devices,
+                                     host_threads, device_blocks, device_done),
+                         n_bad);
 }
 
 // ---- the route model, for callers and tests --------------------------------------------
@@ -3198,10 +3190,11 @@ int stormck_route_set_rates(const stormck_route_rates* rates, uint32_t flags) {
 int stormck_route_devices(const int* devices, int n_devices) {
     std::vector<int> devs;
     if (n_devices != 0) {
-        if (!devices || n_devices < 0 || n_devices > 64) return fail(STORMCK_EINVAL, "devices: 1..64 entries");
-        int rc = device_check();
+        int rc = check_device_list(devices, n_devices);
         if (rc) return rc;
-        rc = check_devices(devices, n_devices, &devs);
+        rc = device_check();
+        if (rc) return rc;
+        rc = check_devices(devices, n_devices, true, &devs);
         if (rc) return rc;
     }
     std::lock_guard<std::mutex> g(g_route_mu);
@@ -3213,14 +3206,14 @@ int stormck_route_plan_batch(uint64_t stride, const uint32_t* lens, uint32_t len
                              uint32_t host_threads, uint32_t n_devices, uint32_t* leg, double* predicted_us) {
     if (!leg) return fail(STORMCK_EINVAL, "leg is null");
     if (memory > STORMCK_MEM_PINNED) return fail(STORMCK_EINVAL, "unknown memory kind");
-    BatchShape s;
-    if (!batch_shape(stride, lens, len, n, &s)) return fail(STORMCK_EINVAL, "stride smaller than a block length (blocks overlap)");
-    const unsigned nt = host_threads ? std::min<unsigned>(host_threads, ForkJoin::get().size()) : ForkJoin::get().size();
-    const uint64_t step = n == 1 ? std::max<uint64_t>(s.longest, 8) : std::max<uint64_t>(stride, 8);
+    HostBatch s;
+    const int rc = measure_batch(stride, lens, len, n, &s);
+    if (rc) return rc;
     const stormck_route_rates rt = RouteModel::get().now();
     const LegPlan p = host_only(rt, static_cast<double>(s.bytes))
                           ? host_only_plan(rt, static_cast<double>(s.bytes))
-                          : plan_batch(rt, n, s, memory == STORMCK_MEM_PINNED, step <= kChunkBytes, nt, n_devices);
+                          : plan_batch(rt, n, s, memory == STORMCK_MEM_PINNED, s.step <= kChunkBytes,
+                                       pool_threads(host_threads), n_devices);
     *leg = n ? p.leg : STORMCK_LEG_NONE;
     if (predicted_us) std::memcpy(predicted_us, p.us, sizeof p.us);
     return STORMCK_OK;
@@ -3231,7 +3224,7 @@ int stormck_route_plan_commit(const stormck_dirty_block* blocks, uint64_t n, uin
     if (!leg) return fail(STORMCK_EINVAL, "leg is null");
     if (memory > STORMCK_MEM_PINNED) return fail(STORMCK_EINVAL, "unknown memory kind");
     if (n > 0 && !blocks) return fail(STORMCK_EINVAL, "blocks is null");
-    const unsigned nt = host_threads ? std::min<unsigned>(host_threads, ForkJoin::get().size()) : ForkJoin::get().size();
+    const unsigned nt = pool_threads(host_threads);
     Heights H;
     if (commit_heights(blocks, n, 0, plan_par(host_threads), &H) != CommitError::Ok)
         return fail(STORMCK_EINVAL, "malformed forest (parent range or cycle)");

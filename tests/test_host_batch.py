@@ -19,6 +19,7 @@ import pytest
 
 from oracle import oracle as o
 from storm_amd import _lib, blocks
+from tests import host_batch_cases as hc
 
 
 def _rows(n, stride, seed, offset=0):
@@ -93,6 +94,17 @@ def test_host_leg_needs_no_device_but_the_routed_batch_does():
         blocks.ChecksumBatch(buf, 4, 64, 64)
     with pytest.raises(_lib.NoDeviceError):
         blocks.VerifyChecksumBatch(buf, 4, 64, [0] * 4, 64)
+
+
+@pytest.mark.parametrize("entry", hc.HOST_LEG)
+def test_host_leg_error_table(entry):
+    """Status, message and first_bad / n_bad of every single-defect call of the host leg
+    (tests/host_batch_cases.py; the other entry points' rows need a device)."""
+    buf = np.zeros(hc.buffer_bytes(), dtype=np.uint8)
+    for case in hc.cases_of(entry):
+        if case == "device_base":
+            continue  # a device pointer: tests/test_host_stage_gpu.py
+        assert hc.run_case(entry, case, buf) == hc.EXPECTED[entry, case], case
 
 
 @pytest.mark.gpu
