@@ -131,6 +131,22 @@ def build_readpeak(force: bool = False) -> str:
     return READPEAK
 
 
+ORDER_PASS = os.path.join(ROOT, "tests", "hip", "liborderpass.so")  # tests/test_gather_order_gpu.py (not product)
+
+
+def build_order_pass(force: bool = False) -> str:
+    """tests/hip/liborderpass.so: the gather's order pass, its scatter and the rank deal on
+    the caller's device buffers (test only; -DSTORMCK_PROBES for k_order_rank)."""
+    srcs = [os.path.join(ROOT, "tests", "hip", "order_pass.hip"), os.path.join(CSRC, "kernels.h"),
+            os.path.join(CSRC, "xxh64_dev.h")]
+    if force or not _newer(ORDER_PASS, srcs):
+        tmp = ORDER_PASS + ".tmp"
+        subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", "-DSTORMCK_PROBES",
+                        "-o", tmp, srcs[0]], check=True)
+        os.replace(tmp, ORDER_PASS)
+    return ORDER_PASS
+
+
 def build_probe(force: bool = False) -> str:
     """Build the design probes (tools/probe*.hip) next to their sources."""
     built = []

@@ -1470,6 +1470,25 @@ __global__ __launch_bounds__(128) void k_order_rank(uint32_t* __restrict__ order
 }
 #endif
 
+// The order pass of one gather on stream st (host side): the bucket totals zeroed, then
+// k_order_count, k_order_scan_buckets, k_order_place and k_order_sort. bounds: 2 *
+// kOrderBuckets words ([first, end) per bucket), cursor: kOrderBuckets words, order, s_offs
+// and (with lens) s_lens: n entries each. Only the offsets' values are read, never what
+// they point at. IDX: the STORMCK_ORDER_IDX variant. A template, so that the kernels are
+// instantiated where the caller asks for them: launch_checksum's code object keeps the
+// layout it had with the launches written out in place.
+template <bool IDX>
+hipError_t order_pass(const uint64_t* offs, const uint32_t* lens, uint64_t n, uint32_t* bounds, uint32_t* cursor,
+                      uint32_t* order, uint64_t* s_offs, uint32_t* s_lens, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(bounds + kOrderBuckets, 0, kOrderBuckets * 4, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_order_count, dim3(kOrderParts), dim3(256), 0, st, offs, n, bounds + kOrderBuckets);
+    hipLaunchKernelGGL(k_order_scan_buckets, dim3(1), dim3(1024), 0, st, bounds, cursor);
+    hipLaunchKernelGGL(k_order_place<IDX>, dim3(kOrderPlaceParts), dim3(256), 0, st, offs, n, cursor, order, s_offs);
+    hipLaunchKernelGGL(k_order_sort<IDX>, dim3(kOrderBuckets), dim3(256), 0, st, lens, bounds, order, s_offs, s_lens, offs);
+    return hipSuccess;
+}
+
 // The stripes of a block that k_xxh64_glds_var did not stage (a start that is not 16-byte
 // aligned), straight from global memory. Out of line: the kernel's hot loop stays compact.
 __device__ __noinline__ uint64_t var_stripes_from_global(const uint8_t* p, uint32_t nst, uint32_t j, uint64_t acc) {

@@ -526,17 +526,12 @@ int launch_checksum(const uint8_t* base, uint64_t stride, const uint32_t* lens, 
             uint64_t* s_out = p.defer ? reinterpret_cast<uint64_t*>(  // 8-byte aligned after the lengths
                                             (reinterpret_cast<uintptr_t>(s_offs + n) + (lens ? n * 4 : 0) + 7) & ~uintptr_t{7})
                                       : nullptr;
-            HIP_TRY(hipMemsetAsync(bounds + kOrderBuckets, 0, kOrderBuckets * 4, st));
-            hipLaunchKernelGGL(k_order_count, dim3(kOrderParts), dim3(256), 0, st, offs, n, bounds + kOrderBuckets);
-            hipLaunchKernelGGL(k_order_scan_buckets, dim3(1), dim3(1024), 0, st, bounds, cursor);
+            hipError_t orc = hipSuccess;
             with_consts([&](auto IDX) {
-                if constexpr (kProbes || !STORMCK_V(IDX)) {
-                    hipLaunchKernelGGL(k_order_place<STORMCK_V(IDX)>, dim3(kOrderPlaceParts), dim3(256), 0, st, offs, n,
-                                       cursor, order, s_offs);
-                    hipLaunchKernelGGL(k_order_sort<STORMCK_V(IDX)>, dim3(kOrderBuckets), dim3(256), 0, st, lens, bounds,
-                                       order, s_offs, s_lens, offs);
-                }
+                if constexpr (kProbes || !STORMCK_V(IDX))
+                    orc = order_pass<STORMCK_V(IDX)>(offs, lens, n, bounds, cursor, order, s_offs, s_lens, st);
             }, p.idx);
+            HIP_TRY(orc);
 #ifdef STORMCK_PROBES
             if (p.rank)
                 hipLaunchKernelGGL(k_order_rank, dim3(static_cast<unsigned>(n / kGldsBlocks)), dim3(kGldsBlocks), 0, st,

@@ -161,6 +161,23 @@ static void lengths_and_gathers() {
     // a scrub level of 11,300 leaves and two pointer blocks (tests/test_scrub_damage_gpu.py): offsets and
     // lengths bounded by 32 KiB; 707 one-wave workgroups -> 3 x 16 and 236 three-wave ones -> 48: the tie
     expect("scrub level n=11302", plan(short_gather(11302, 32768, true)), Kernel::GldsVar, 236, 192, 3);
+    // the four ordered gathers of tests/test_gather_order_gpu.py, n = 2^20 + 37: 8,193 workgroups,
+    // 33 on the busiest CU. Per-block lengths: bound 0 plans 32 KiB = 64 tile steps, 33 x 64 = 2,112 <
+    // 3,584; bound 65,536 = 128 steps, 4,224: persistent. One length: 4,112 B = 9 steps; 60,000 B =
+    // 118 steps, 3,894: persistent.
+    const uint64_t n_ord = (uint64_t{1} << 20) + 37;
+    struct { const char* what; uint32_t len; bool lens, persistent; } ordered[] = {
+        {"ordered gather+lens bound 0", 0, true, false},
+        {"ordered gather+lens bound 65536", 65536, true, true},
+        {"ordered gather len=4112", 4112, false, false},
+        {"ordered gather len=60000", 60000, false, true},
+    };
+    for (const auto& c : ordered) {
+        const Plan p = plan(short_gather(n_ord, c.len, c.lens));
+        expect(c.what, p, Kernel::GldsVarOrdered, c.persistent ? 256 : 8193, 512, 8);
+        expect_true(std::string(c.what) + ": persistent flag, shipped variants",
+                    p.persistent == c.persistent && !p.defer && !p.idx && !p.rank && !p.contig);
+    }
     // strided rows 512 KiB apart, 4,099 bytes each
     auto far_rows = [](uint64_t n) {
         Query q = uniform(n, 4099);
