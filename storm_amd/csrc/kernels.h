@@ -246,6 +246,56 @@ __device__ __forceinline__ uint64_t finish_lds16(uint64_t h, uint64_t n, const u
     return finish_regs(h, n, w, rem);
 }
 
+// The four accumulators of a quad, in every lane of it (quad_bcast: all four lanes must
+// be active, so the merge stands outside the branch that only lane 0 of a live quad takes).
+struct QuadAcc {
+    uint64_t v1, v2, v3, v4;
+    // XXH64's value before the tail: the merged accumulators from 32 bytes on.
+    __device__ __forceinline__ uint64_t start(uint32_t len) const {
+        return (len >= 32) ? converge(v1, v2, v3, v4) : kP5;
+    }
+};
+__device__ __forceinline__ QuadAcc quad_merge(uint64_t acc) {
+    return {quad_bcast<0>(acc), quad_bcast<1>(acc), quad_bcast<2>(acc), quad_bcast<3>(acc)};
+}
+
+// The stripes of a block at any alignment, straight from memory (lane j of the quad).
+template <int U>
+__device__ __forceinline__ uint64_t quad_stripes_any(const uint8_t* p, uint32_t nst, uint32_t j, uint64_t acc) {
+    if ((reinterpret_cast<uintptr_t>(p) & 7) == 0)
+        return quad_stripes_aligned<U>(reinterpret_cast<const uint64_t*>(p) + j, nst, acc);
+    return quad_stripes_unaligned(p + 8 * j, nst, acc);
+}
+
+// A mismatch of a verify launch: lower *first_bad to the block's index, count it in *n_bad.
+__device__ __forceinline__ void count_bad(uint64_t idx, unsigned long long* first_bad, unsigned long long* n_bad) {
+    atomicMin(first_bad, static_cast<unsigned long long>(idx));
+    atomicAdd(n_bad, 1ULL);
+}
+
+// Where a checksum goes. VERIFY: compared with expected[idx], a mismatch counted; else out[idx].
+template <bool VERIFY>
+__device__ __forceinline__ void put_checksum(uint64_t h, uint64_t idx, uint64_t* out, const uint64_t* expected,
+                                             unsigned long long* first_bad, unsigned long long* n_bad) {
+    if constexpr (VERIFY) {
+        if (h != expected[idx]) count_bad(idx, first_bad, n_bad);
+    } else {
+        out[idx] = h;
+    }
+}
+
+// storm's PostCommitFunc (cache/trace.go:274-320) for a hashed dirty block: Pointer{cs,
+// address, birth_revision} into the parent's origin slot, the block type into its type byte.
+__device__ __forceinline__ void post_commit(uint8_t* arena, const stormck_dirty_block& rec, uint64_t h) {
+    if (rec.origin_pointer != STORMCK_NO_ORIGIN) {
+        uint64_t* p = reinterpret_cast<uint64_t*>(arena + rec.origin_pointer);
+        p[0] = h;
+        p[1] = rec.address;
+        p[2] = rec.birth_revision;
+        arena[rec.origin_type] = rec.type;
+    }
+}
+
 // ---------------------------------------------------------------------------
 // Quad kernel: 4 lanes per block. Block i starts at base + (OFFS ? offs[i] : i*stride)
 // and is LENS ? lens[i] : len bytes long. 256-thread workgroups = 64 blocks.
@@ -279,21 +329,10 @@ __global__ __launch_bounds__(TH) void k_xxh64_quad(const uint8_t* __restrict__ b
     } else {
         acc = quad_stripes_unaligned(src + 8 * j, nst, acc);
     }
-    const uint64_t v1 = quad_bcast<0>(acc);
-    const uint64_t v2 = quad_bcast<1>(acc);
-    const uint64_t v3 = quad_bcast<2>(acc);
-    const uint64_t v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0 && live) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        const uint64_t h = finish_fast(h0, L, src + 32 * static_cast<uint64_t>(nst), L & 31);
-        if (VERIFY) {
-            if (h != expected[blk]) {
-                atomicMin(first_bad, static_cast<unsigned long long>(blk));
-                atomicAdd(n_bad, 1ULL);
-            }
-        } else {
-            out[blk] = h;
-        }
+        const uint64_t h = finish_fast(q.start(L), L, src + 32 * static_cast<uint64_t>(nst), L & 31);
+        put_checksum<VERIFY>(h, blk, out, expected, first_bad, n_bad);
     }
 }
 
@@ -385,11 +424,8 @@ __global__ __launch_bounds__(256) void k_xxh64_single(const uint8_t* __restrict_
     const uint32_t j = threadIdx.x;
     const uint8_t* s = reinterpret_cast<const uint8_t*>(buf);
     const uint64_t acc = quad_stripes_aligned<16, false, true>(reinterpret_cast<const uint64_t*>(s) + j, nst, acc_seed(j));
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
-    if (j == 0) {
-        const uint64_t h0 = (n >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        *out = finish_fast(h0, n, s + 32 * nst, n & 31);
-    }
+    const QuadAcc q = quad_merge(acc);
+    if (j == 0) *out = finish_fast(q.start(n), n, s + 32 * nst, n & 31);
 }
 
 // ---------------------------------------------------------------------------
@@ -447,23 +483,13 @@ __device__ __forceinline__ void wide_hash(const uint8_t* s, uint32_t L, uint64_t
     uint64_t acc = acc_seed(j);
     if constexpr (PM) {  // staged with premultiplied stripe words, 8-byte aligned
         acc = quad_stripes_aligned<16, false, true>(reinterpret_cast<const uint64_t*>(s) + j, nst, acc);
-    } else if ((reinterpret_cast<uintptr_t>(s) & 7) == 0) {
-        acc = quad_stripes_aligned<16>(reinterpret_cast<const uint64_t*>(s) + j, nst, acc);
     } else {
-        acc = quad_stripes_unaligned(s + 8 * j, nst, acc);
+        acc = quad_stripes_any<16>(s, nst, j, acc);
     }
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        const uint64_t h = finish_fast(h0, L, s + 32 * static_cast<uint64_t>(nst), L & 31);
-        if (VERIFY) {
-            if (h != expected[blk]) {
-                atomicMin(first_bad, static_cast<unsigned long long>(blk));
-                atomicAdd(n_bad, 1ULL);
-            }
-        } else {
-            out[blk] = h;
-        }
+        const uint64_t h = finish_fast(q.start(L), L, s + 32 * static_cast<uint64_t>(nst), L & 31);
+        put_checksum<VERIFY>(h, blk, out, expected, first_bad, n_bad);
     }
 }
 
@@ -604,15 +630,10 @@ __device__ __forceinline__ void multi_stage_hash(uint4* buf, uint32_t nlive, Src
     uint64_t acc = acc_seed(j);
     if (staged)
         acc = quad_stripes_aligned<16, false, true>(reinterpret_cast<const uint64_t*>(s) + j, nst, acc);
-    else if ((reinterpret_cast<uintptr_t>(src) & 7) == 0)
-        acc = quad_stripes_aligned<16>(reinterpret_cast<const uint64_t*>(src) + j, nst, acc);
     else
-        acc = quad_stripes_unaligned(src + 8 * j, nst, acc);
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
-    if (j == 0 && live) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        emit(b, finish_fast(h0, L, s + 32 * static_cast<uint64_t>(nst), L & 31));
-    }
+        acc = quad_stripes_any<16>(src, nst, j, acc);
+    const QuadAcc q = quad_merge(acc);
+    if (j == 0 && live) emit(b, finish_fast(q.start(L), L, s + 32 * static_cast<uint64_t>(nst), L & 31));
 }
 
 // Pipelined form of multi_stage_hash. The whole-block staging above costs one full
@@ -856,12 +877,7 @@ __device__ __forceinline__ void multi_stage_hash_pipe(uint4* ring, const PipeCtl
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         if (threadIdx.x == 0) __hip_atomic_store(done, c + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-    if (!staged) {
-        if ((reinterpret_cast<uintptr_t>(src) & 7) == 0)
-            acc = quad_stripes_aligned<16>(reinterpret_cast<const uint64_t*>(src) + j, nst, acc);
-        else
-            acc = quad_stripes_unaligned(src + 8 * j, nst, acc);
-    }
+    if (!staged) acc = quad_stripes_any<16>(src, nst, j, acc);
     // a stager that gave up (its wait for `done` expired) also voids the workgroup:
     // it may have left a slot unwritten that the chain already passed
     if (__hip_atomic_load(pc.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) ok = false;
@@ -869,9 +885,10 @@ __device__ __forceinline__ void multi_stage_hash_pipe(uint4* ring, const PipeCtl
         if (j == 0 && live) void_block(b);
         return;
     }
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0 && live) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
+        // (q.start(L) written out: through the call the two multi kernels compile to other instructions)
+        const uint64_t h0 = (L >= 32) ? converge(q.v1, q.v2, q.v3, q.v4) : kP5;
         emit(b, staged ? finish_regs(h0, L, tail, L & 31)
                        : finish_fast(h0, L, src + 32 * static_cast<uint64_t>(nst), L & 31));
     }
@@ -897,26 +914,13 @@ __global__ __launch_bounds__(256) void k_xxh64_wide_multi(const uint8_t* __restr
         const uint64_t blk = first + b;
         return BlockRef{base + (OFFS ? offs[blk] : blk * stride), LENS ? lens[blk] : len};
     };
-    auto emit = [&](uint32_t b, uint64_t h) {
-        const uint64_t blk = first + b;
-        if (VERIFY) {
-            if (h != expected[blk]) {
-                atomicMin(first_bad, static_cast<unsigned long long>(blk));
-                atomicAdd(n_bad, 1ULL);
-            }
-        } else {
-            out[blk] = h;
-        }
-    };
+    auto emit = [&](uint32_t b, uint64_t h) { put_checksum<VERIFY>(h, first + b, out, expected, first_bad, n_bad); };
     if constexpr (RING > 0) {
         __shared__ uint4 ring[BPW * ring_block_pieces(RING, CP) + kRingSlackPieces];
         __shared__ uint32_t ready[pipe_max_chunks(CP)], done[1], abort_w[1];
         const PipeCtl pc{ready, done, abort_w, fault, kFaultWideMulti, stall};
         auto void_block = [&](uint32_t b) {
-            if (VERIFY) {  // fail closed: an unhashed block is a mismatch
-                atomicMin(first_bad, static_cast<unsigned long long>(first + b));
-                atomicAdd(n_bad, 1ULL);
-            }
+            if (VERIFY) count_bad(first + b, first_bad, n_bad);  // fail closed: an unhashed block is a mismatch
         };
         multi_stage_hash_pipe<BPW, RING, CP, DBL>(ring, pc, nlive, src_of, emit, void_block);
     } else {
@@ -944,6 +948,32 @@ __device__ __forceinline__ uint32_t glds_rot(uint32_t b) {
     else return (2 * (b / (8 / T))) % pieces;
 }
 
+// The tile of a workgroup of WAVES waves: T stripes of each of its blocks.
+template <int T, int WAVES>
+struct GldsTile {
+    static constexpr int BPW = 16 * WAVES;         // blocks per workgroup (a quad of lanes per block)
+    static constexpr int ROW = 32 * T;             // bytes per block per tile
+    static constexpr int TILE = BPW * ROW;         // bytes per tile
+    static constexpr int INSTR = TILE / 1024;      // glds wave-instructions per tile (whole workgroup)
+    static constexpr int PER_WAVE = INSTR / WAVES; // ... per wave
+    static_assert(INSTR % WAVES == 0, "tile must split evenly over the waves");
+};
+
+// Piece geometry: instruction K of this wave fills 1 KiB of the tile image, 16 bytes per
+// lane. Declares B_ = the block row this lane's piece lies in and P_ = the 16-byte piece
+// of that block's row it holds (the rotated source piece). T, ROW, PER_WAVE, wave and
+// lane are the kernel's. A macro, as the read below: written as functions, both change
+// the instruction streams of the kernels that use them (DESIGN_LOG.md §18).
+#define STORMCK_GLDS_PIECE(K, B_, P_)                                                            \
+    const uint32_t off_ = (wave * PER_WAVE + (K)) * 1024 + lane * 16; /* byte in the tile image */ \
+    const uint32_t B_ = off_ / ROW, q_ = (off_ % ROW) / 16;           /* block row, LDS piece */    \
+    const uint32_t P_ = (q_ + glds_rot<T>(B_)) % (2 * T)
+
+// The rotated row read: word j of stripe S of the block row whose rotation is `rot`, from
+// ROWP = the row's first byte in the tile + (j & 1) * 8 (T, j and rot are the kernel's).
+#define STORMCK_GLDS_WORD(ROWP, S) \
+    (*reinterpret_cast<const uint64_t*>((ROWP) + ((2 * (S) + (j >> 1) + 2 * T - rot) % (2 * T)) * 16))
+
 // One tile's worth of this wave's LDS-DMA pieces: instruction k moves 64 x 16 B from
 // the lanes' sources (advanced by t tiles) to dst + k*1024 (lane-linear). A macro:
 // the builtin's size/aux operands must stay literal constants.
@@ -964,12 +994,8 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds(const uint8_t* __rest
                                                      const uint64_t* __restrict__ expected = nullptr,
                                                      unsigned long long* __restrict__ first_bad = nullptr,
                                                      unsigned long long* __restrict__ n_bad = nullptr) {
-    constexpr int BPW = 16 * WAVES;         // blocks per workgroup (a quad of lanes per block)
-    constexpr int ROW = 32 * T;             // bytes per block per tile
-    constexpr int TILE = BPW * ROW;         // bytes per tile
-    constexpr int INSTR = TILE / 1024;      // glds wave-instructions per tile (whole workgroup)
-    constexpr int PER_WAVE = INSTR / WAVES; // ... per wave
-    static_assert(INSTR % WAVES == 0, "tile must split evenly over the waves");
+    using Tile = GldsTile<T, WAVES>;
+    constexpr int BPW = Tile::BPW, ROW = Tile::ROW, TILE = Tile::TILE, PER_WAVE = Tile::PER_WAVE;
     static_assert(R >= 2, "ring needs >= 2 slots");
     static_assert(SYNC || T % 2 == 0, "without SYNC a wave's pieces must be its own block rows");
     __shared__ __attribute__((aligned(16))) uint8_t lds[R * TILE];
@@ -989,13 +1015,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds(const uint8_t* __rest
     const uint8_t* src[PER_WAVE];
 #pragma unroll
     for (int k = 0; k < PER_WAVE; ++k) {
-        const uint32_t ii = wave * PER_WAVE + k;            // instruction index within the tile
-        const uint32_t off = ii * 1024 + lane * 16;          // byte offset in the tile image
-        const uint32_t b = off / ROW, q = (off % ROW) / 16;  // block row, LDS piece
-        const uint32_t p = (q + glds_rot<T>(b)) % (2 * T);  // source piece
-        uint64_t gb = blk0 + b;
-        if (gb >= n) gb = n - 1;                             // shadow the last block; never stored
-        src[k] = base + gb * stride + p * 16;
+        STORMCK_GLDS_PIECE(k, prow, piece);
+        uint64_t gb = blk0 + prow;
+        if (gb >= n) gb = n - 1;  // shadow the last block; never stored
+        src[k] = base + gb * stride + piece * 16;
     }
 
     const uint32_t b = tid >> 2, j = tid & 3;
@@ -1023,8 +1046,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds(const uint8_t* __rest
         const uint8_t* row = lds + (t % R) * TILE + b * ROW + (j & 1) * 8;
 #pragma unroll
         for (int s = 0; s < T; ++s) {
-            const uint32_t q = (2 * s + (j >> 1) + 2 * T - rot) % (2 * T);
-            const uint64_t w = *reinterpret_cast<const uint64_t*>(row + q * 16);
+            const uint64_t w = STORMCK_GLDS_WORD(row, s);
             if constexpr (HASH) acc = round(acc, w);
             else acc ^= w;  // measurement control: same data movement, no hash arithmetic
         }
@@ -1035,18 +1057,10 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds(const uint8_t* __rest
     const uint8_t* blk_src = base + gb * stride;
     for (uint32_t s = ntiles * T; s < nst; ++s)
         acc = round(acc, reinterpret_cast<const uint64_t*>(blk_src)[4 * s + j]);
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0 && gbk < n) {
-        const uint64_t h0 = (len >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        const uint64_t h = finish_fast(h0, len, blk_src + 32 * static_cast<uint64_t>(nst), len & 31);
-        if constexpr (VERIFY) {
-            if (h != expected[gbk]) {
-                atomicMin(first_bad, static_cast<unsigned long long>(gbk));
-                atomicAdd(n_bad, 1ULL);
-            }
-        } else {
-            out[gbk] = h;
-        }
+        const uint64_t h = finish_fast(q.start(len), len, blk_src + 32 * static_cast<uint64_t>(nst), len & 31);
+        put_checksum<VERIFY>(h, gbk, out, expected, first_bad, n_bad);
     }
 }
 
@@ -1071,12 +1085,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_skew(const uint8_t* _
                                                                 const uint64_t* __restrict__ expected,
                                                                 unsigned long long* __restrict__ first_bad,
                                                                 unsigned long long* __restrict__ n_bad) {
-    constexpr int BPW = 16 * WAVES;
-    constexpr int ROW = 32 * T;
-    constexpr int TILE = BPW * ROW;
-    constexpr int INSTR = TILE / 1024;
-    constexpr int PER_WAVE = INSTR / WAVES;
-    static_assert(INSTR % WAVES == 0 && T % 2 == 0, "a wave's pieces must be its own block rows");
+    using Tile = GldsTile<T, WAVES>;
+    constexpr int BPW = Tile::BPW, ROW = Tile::ROW, TILE = Tile::TILE, PER_WAVE = Tile::PER_WAVE;
+    static_assert(T % 2 == 0, "a wave's pieces must be its own block rows");
     __shared__ __attribute__((aligned(16))) uint8_t lds[2 * TILE];
 
     const uint32_t tid = threadIdx.x;
@@ -1093,10 +1104,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_skew(const uint8_t* _
     uint32_t prow[PER_WAVE], pofs[PER_WAVE];
 #pragma unroll
     for (int k = 0; k < PER_WAVE; ++k) {
-        const uint32_t off = (wave * PER_WAVE + k) * 1024 + lane * 16;
-        const uint32_t b = off / ROW, q = (off % ROW) / 16;
-        prow[k] = b;
-        pofs[k] = ((q + glds_rot<T>(b)) % (2 * T)) * 16;
+        STORMCK_GLDS_PIECE(k, row, piece);
+        prow[k] = row;
+        pofs[k] = piece * 16;
     }
     const uint8_t* src[PER_WAVE];
     uint64_t ig = blockIdx.x, hg = blockIdx.x, ic = 0, hc = 0;  // issue / hash: group, tiles done
@@ -1129,8 +1139,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_skew(const uint8_t* _
             const uint8_t* row = lds + (u & 1) * TILE + b * ROW + (j & 1) * 8;
 #pragma unroll
             for (int s = 0; s < T; ++s) {
-                const uint32_t q = (2 * s + (j >> 1) + 2 * T - rot) % (2 * T);
-                const uint64_t w = *reinterpret_cast<const uint64_t*>(row + q * 16);
+                const uint64_t w = STORMCK_GLDS_WORD(row, s);
                 if constexpr (HASH) acc = round(acc, w);
                 else acc ^= w;
             }
@@ -1142,19 +1151,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_skew(const uint8_t* _
                 const uint8_t* blk_src = base + gb * stride;
                 for (uint32_t s = ntiles * T; s < nst; ++s)
                     acc = round(acc, reinterpret_cast<const uint64_t*>(blk_src)[4 * s + j]);
-                const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc),
-                               v4 = quad_bcast<3>(acc);
+                const QuadAcc q = quad_merge(acc);
                 if (j == 0 && gbk < n) {
-                    const uint64_t h = finish_fast(converge(v1, v2, v3, v4), len,
+                    // (whole tiles were hashed: len >= 32)
+                    const uint64_t h = finish_fast(converge(q.v1, q.v2, q.v3, q.v4), len,
                                                    blk_src + 32 * static_cast<uint64_t>(nst), len & 31);
-                    if constexpr (VERIFY) {
-                        if (h != expected[gbk]) {
-                            atomicMin(first_bad, static_cast<unsigned long long>(gbk));
-                            atomicAdd(n_bad, 1ULL);
-                        }
-                    } else {
-                        out[gbk] = h;
-                    }
+                    put_checksum<VERIFY>(h, gbk, out, expected, first_bad, n_bad);
                 }
                 acc = acc_seed(j);
                 ht = 0;
@@ -1492,9 +1494,7 @@ hipError_t order_pass(const uint64_t* offs, const uint32_t* lens, uint64_t n, ui
 // The stripes of a block that k_xxh64_glds_var did not stage (a start that is not 16-byte
 // aligned), straight from global memory. Out of line: the kernel's hot loop stays compact.
 __device__ __noinline__ uint64_t var_stripes_from_global(const uint8_t* p, uint32_t nst, uint32_t j, uint64_t acc) {
-    if ((reinterpret_cast<uintptr_t>(p) & 7) == 0)
-        return quad_stripes_aligned<16>(reinterpret_cast<const uint64_t*>(p) + j, nst, acc);
-    return quad_stripes_unaligned(p + 8 * j, nst, acc);
+    return quad_stripes_any<16>(p, nst, j, acc);
 }
 
 // ORD: offs and lens are in a locality order of a large gather (k_order_*, s_offs /
@@ -1510,12 +1510,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_var(const uint8_t* __
                                                                unsigned long long* __restrict__ first_bad,
                                                                unsigned long long* __restrict__ n_bad,
                                                                const uint32_t* __restrict__ order = nullptr) {
-    constexpr int BPW = 16 * WAVES;
-    constexpr int ROW = 32 * T;
-    constexpr int TILE = BPW * ROW;
-    constexpr int INSTR = TILE / 1024;
-    constexpr int PER_WAVE = INSTR / WAVES;
-    static_assert(INSTR % WAVES == 0 && T % 2 == 0 && WAVES <= 8, "a wave's pieces must be its own block rows");
+    using Tile = GldsTile<T, WAVES>;
+    constexpr int BPW = Tile::BPW, ROW = Tile::ROW, TILE = Tile::TILE, PER_WAVE = Tile::PER_WAVE;
+    static_assert(T % 2 == 0 && WAVES <= 8, "a wave's pieces must be its own block rows");
     // the ring, then the count of waves whose stream has ended (in the same array: a
     // second __shared__ array makes hipcc guard ds_reads after an LDS-DMA with vmcnt(0),
     // k_commit_level_glds)
@@ -1550,10 +1547,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_var(const uint8_t* __
     uint32_t prow[PER_WAVE], pofs[PER_WAVE];
 #pragma unroll
     for (int k = 0; k < PER_WAVE; ++k) {
-        const uint32_t off = (wave * PER_WAVE + k) * 1024 + lane * 16;
-        const uint32_t b = off / ROW, q = (off % ROW) / 16;
-        prow[k] = b;
-        pofs[k] = ((q + glds_rot<T>(b)) % (2 * T)) * 16;
+        STORMCK_GLDS_PIECE(k, row, piece);
+        prow[k] = row;
+        pofs[k] = piece * 16;
     }
     const uint8_t* i_src[PER_WAVE];
     uint32_t i_lim[PER_WAVE];
@@ -1673,20 +1669,12 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_var(const uint8_t* __
     };
     auto h_finish = [&]() __attribute__((always_inline)) {  // the group's blocks are complete: unstaged stripes, tail, checksum
         if (__builtin_expect(h_sst < h_nst, 0)) acc = var_stripes_from_global(h_p, h_nst, j, acc);
-        const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+        const QuadAcc q = quad_merge(acc);
         if (j == 0 && h_live) {
-            const uint64_t gbk = h_idx;
-            const uint64_t h0 = (h_L >= 32) ? converge(v1, v2, v3, v4) : kP5;
+            const uint64_t h0 = q.start(h_L);
             const uint64_t h = h_sst == h_nst && h_L >= 32 ? finish_regs(h0, h_L, tail, h_L & 31)
                                                            : finish_fast(h0, h_L, h_p + 32 * static_cast<uint64_t>(h_nst), h_L & 31);
-            if constexpr (VERIFY) {
-                if (h != expected[gbk]) {
-                    atomicMin(first_bad, static_cast<unsigned long long>(gbk));
-                    atomicAdd(n_bad, 1ULL);
-                }
-            } else {
-                out[gbk] = h;
-            }
+            put_checksum<VERIFY>(h, h_idx, out, expected, first_bad, n_bad);
         }
     };
     auto h_next_group = [&]() __attribute__((always_inline)) {  // finish groups without tiles on the way
@@ -1744,10 +1732,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_xxh64_glds_var(const uint8_t* __
             // would put each LDS read in its own branch and wait for it there
             uint64_t w[T];
 #pragma unroll
-            for (int s = 0; s < T; ++s) {
-                const uint32_t q = (2 * s + (j >> 1) + 2 * T - rot) % (2 * T);
-                w[s] = *reinterpret_cast<const uint64_t*>(row + q * 16);
-            }
+            for (int s = 0; s < T; ++s) w[s] = STORMCK_GLDS_WORD(row, s);
             if (__builtin_expect(s0 + T <= h_sst, 1)) {
 #pragma unroll
                 for (int s = 0; s < T; ++s) acc = round(acc, w[s]);
@@ -1846,8 +1831,7 @@ __device__ __forceinline__ uint64_t hash_words_quad(const W& word, uint32_t size
         s = ngroups * U;
     }
     for (; s < nst; ++s) acc = rnd(acc, word(4 * s + j));
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
-    uint64_t h = (size >= 32) ? converge(v1, v2, v3, v4) : kP5;
+    uint64_t h = quad_merge(acc).start(size);
     h += size;
     for (uint32_t k = 4 * nst; k < size / 8; ++k) {
         h ^= round(0, word(k));
@@ -1992,8 +1976,7 @@ __device__ __forceinline__ void ring_finish(uint64_t acc, uint32_t j, uint64_t n
     } else {
         for (uint32_t s = kPtrStripes; s < kNst; ++s) acc = round(acc, type_word(4 * (s - kPtrStripes) + j));
     }
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
-    uint64_t h = converge(v1, v2, v3, v4) + kSize;
+    uint64_t h = quad_merge(acc).start(kSize) + kSize;
     for (uint32_t k = 4 * kNst; k < kWords; ++k) {
         h ^= round(0, type_word(k - 3 * F));
         h = rotl<27>(h) * kP1 + kP4;
@@ -2227,23 +2210,17 @@ __global__ __launch_bounds__(256) void k_commit_level_wide(uint8_t* __restrict__
     } else {
         if (j >= 4) return;
         s = src;
+        // (not quad_stripes_any: through it the tail's loads compile to other instructions)
         if ((reinterpret_cast<uintptr_t>(s) & 7) == 0)
             acc = quad_stripes_aligned<16>(reinterpret_cast<const uint64_t*>(s) + j, nst, acc);
         else
             acc = quad_stripes_unaligned(s + 8 * j, nst, acc);
     }
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        const uint64_t h = finish_fast(h0, L, s + 32 * static_cast<uint64_t>(nst), L & 31);
+        const uint64_t h = finish_fast(q.start(L), L, s + 32 * static_cast<uint64_t>(nst), L & 31);
         out_cs[k] = h;
-        if (b.origin_pointer != STORMCK_NO_ORIGIN) {
-            uint64_t* p = reinterpret_cast<uint64_t*>(arena + b.origin_pointer);
-            p[0] = h;
-            p[1] = b.address;
-            p[2] = b.birth_revision;
-            arena[b.origin_type] = b.type;
-        }
+        post_commit(arena, b, h);
     }
 }
 
@@ -2271,15 +2248,8 @@ __global__ __launch_bounds__(256) void k_commit_level_multi(uint8_t* __restrict_
     const stormck_dirty_block* rec = reinterpret_cast<const stormck_dirty_block*>(rec_w);
     auto src_of = [&](uint32_t b) { return BlockRef{arena + rec[b].data_offset, rec[b].length}; };
     auto emit = [&](uint32_t b, uint64_t h) {
-        const stormck_dirty_block& r = rec[b];
         out_cs[lo + first + b] = h;
-        if (r.origin_pointer != STORMCK_NO_ORIGIN) {
-            uint64_t* p = reinterpret_cast<uint64_t*>(arena + r.origin_pointer);
-            p[0] = h;
-            p[1] = r.address;
-            p[2] = r.birth_revision;
-            arena[r.origin_type] = r.type;
-        }
+        post_commit(arena, rec[b], h);
     };
     if constexpr (RING > 0) {
         __shared__ uint4 ring[BPW * ring_block_pieces(RING, CP) + kRingSlackPieces];
@@ -2306,22 +2276,16 @@ __global__ __launch_bounds__(256) void k_commit_level(uint8_t* __restrict__ aren
     const uint32_t L = b.length;
     const uint32_t nst = L >> 5;
     uint64_t acc = acc_seed(j);
+    // (not quad_stripes_any: through it the tail's loads compile to other instructions)
     if ((reinterpret_cast<uintptr_t>(src) & 7) == 0)
         acc = quad_stripes_aligned<U>(reinterpret_cast<const uint64_t*>(src) + j, nst, acc);
     else
         acc = quad_stripes_unaligned(src + 8 * j, nst, acc);
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0 && live) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        const uint64_t h = finish_fast(h0, L, src + 32 * static_cast<uint64_t>(nst), L & 31);
+        const uint64_t h = finish_fast(q.start(L), L, src + 32 * static_cast<uint64_t>(nst), L & 31);
         out_cs[lo + kk] = h;
-        if (b.origin_pointer != STORMCK_NO_ORIGIN) {
-            uint64_t* p = reinterpret_cast<uint64_t*>(arena + b.origin_pointer);
-            p[0] = h;
-            p[1] = b.address;
-            p[2] = b.birth_revision;
-            arena[b.origin_type] = b.type;
-        }
+        post_commit(arena, b, h);
     }
 }
 
@@ -2343,13 +2307,9 @@ __global__ __launch_bounds__(64 * WAVES) void k_commit_level_glds(uint8_t* __res
                                                                    uint64_t lo, uint64_t cnt,
                                                                    uint64_t* __restrict__ out_cs) {
     constexpr int R = 2;
-    constexpr int BPW = 16 * WAVES;
-    constexpr int ROW = 32 * T;
-    constexpr int TILE = BPW * ROW;
-    constexpr int INSTR = TILE / 1024;
-    constexpr int PER_WAVE = INSTR / WAVES;
+    using Tile = GldsTile<T, WAVES>;
+    constexpr int BPW = Tile::BPW, ROW = Tile::ROW, TILE = Tile::TILE, PER_WAVE = Tile::PER_WAVE;
     constexpr int RW = sizeof(stormck_dirty_block) / 8;  // 7 words per record
-    static_assert(INSTR % WAVES == 0, "tile must split evenly over the waves");
     __shared__ __attribute__((aligned(16))) uint8_t lds[R * TILE];
     // the records sit in ring slot 1 until the first tile is issued into it. (A second
     // __shared__ array makes hipcc guard every ds_read after an LDS-DMA with vmcnt(0),
@@ -2383,10 +2343,7 @@ __global__ __launch_bounds__(64 * WAVES) void k_commit_level_glds(uint8_t* __res
     uint32_t ntl[PER_WAVE];
 #pragma unroll
     for (int k = 0; k < PER_WAVE; ++k) {
-        const uint32_t ii = wave * PER_WAVE + k;
-        const uint32_t off = ii * 1024 + lane * 16;
-        const uint32_t bb = off / ROW, q = (off % ROW) / 16;
-        const uint32_t piece = (q + glds_rot<T>(bb)) % (2 * T);
+        STORMCK_GLDS_PIECE(k, bb, piece);
         const bool plive = bb < nrec;
         const stormck_dirty_block& r = recs[plive ? bb : 0];
         src[k] = arena + r.data_offset + piece * 16;
@@ -2430,27 +2387,17 @@ __global__ __launch_bounds__(64 * WAVES) void k_commit_level_glds(uint8_t* __res
         if (t < my_tiles) {
             const uint8_t* row = lds + (t & 1) * TILE + b * ROW + (j & 1) * 8;
 #pragma unroll
-            for (int s = 0; s < T; ++s) {
-                const uint32_t q = (2 * s + (j >> 1) + 2 * T - rot) % (2 * T);
-                acc = round(acc, *reinterpret_cast<const uint64_t*>(row + q * 16));
-            }
+            for (int s = 0; s < T; ++s) acc = round(acc, STORMCK_GLDS_WORD(row, s));
         }
     }
 #undef STORMCK_GLDS_ISSUE_MASKED
     const uint8_t* bsrc = arena + rec.data_offset;
     for (uint32_t s = my_tiles * T; s < nst; ++s) acc = round(acc, reinterpret_cast<const uint64_t*>(bsrc)[4 * s + j]);
-    const uint64_t v1 = quad_bcast<0>(acc), v2 = quad_bcast<1>(acc), v3 = quad_bcast<2>(acc), v4 = quad_bcast<3>(acc);
+    const QuadAcc q = quad_merge(acc);
     if (j == 0 && live) {
-        const uint64_t h0 = (L >= 32) ? converge(v1, v2, v3, v4) : kP5;
-        const uint64_t h = finish_fast(h0, L, bsrc + 32 * static_cast<uint64_t>(nst), L & 31);
+        const uint64_t h = finish_fast(q.start(L), L, bsrc + 32 * static_cast<uint64_t>(nst), L & 31);
         out_cs[lo + kb] = h;
-        if (rec.origin_pointer != STORMCK_NO_ORIGIN) {
-            uint64_t* p = reinterpret_cast<uint64_t*>(arena + rec.origin_pointer);
-            p[0] = h;
-            p[1] = rec.address;
-            p[2] = rec.birth_revision;
-            arena[rec.origin_type] = rec.type;
-        }
+        post_commit(arena, rec, h);
     }
 }
 
