@@ -33,6 +33,7 @@
 #include "commit_plan.h"
 #include "dispatch.h"
 #include "kernels.h"
+#include "route_plan.h"
 #include "xxh64_host.h"
 
 using namespace stormck;
@@ -187,11 +188,21 @@ class ForkJoin {
     const std::function<void(unsigned)>* job_ = nullptr;
 };
 
-// Host threads a call may use: `threads` of the pool (0 = the pool).
-unsigned pool_threads(uint32_t threads) {
-    const unsigned size = ForkJoin::get().size();
-    return threads ? std::min<unsigned>(threads, size) : size;
+// The pool as a call allowed host_threads threads (0 = the pool) finds it. routed: a call that
+// may use the pool asks how long another call's job holds it (route_plan.h route_on); the
+// plan entry points price a free pool.
+Pool pool_facts(uint32_t host_threads, bool routed) {
+    ForkJoin& fj = ForkJoin::get();
+    Pool p;
+    p.size = fj.size();
+    p.cpus = fj.cpus();
+    p.threads = host_threads ? std::min<unsigned>(host_threads, p.size) : p.size;
+    p.busy_us = routed && p.threads > 1 ? fj.busy_for_us() : 0.0;
+    return p;
 }
+
+// Host threads a call may use: `threads` of the pool (0 = the pool).
+unsigned pool_threads(uint32_t threads) { return pool_facts(threads, false).threads; }
 
 int fail(int code, const std::string& msg) {
     g_last_error = msg;
@@ -630,6 +641,7 @@ __global__ void k_init_result(uint64_t* r, uint64_t n) {
 
 // ---- per-device context for the host-memory path ---------------------------------
 constexpr uint64_t kChunkBytes = 256ULL << 20;  // bytes of block data per pipeline stage
+static_assert(kStageChunkBytes == kChunkBytes, "route_plan.h prices the staging chunk of the stages");
 constexpr int kStages = 2;
 
 struct Stage {
@@ -2071,165 +2083,15 @@ int commit_device_run(void* d_arena, stormck_dirty_block* blocks, const Heights&
 }  // namespace
 
 // ---- routing of host-memory work: host, device and split legs ------------------------
-// Work that lives in host memory (storm's cache.data: the Go shim's ChecksumBatch,
-// VerifyChecksumBatch and CommitBatch) runs on one of three legs:
-//   host    the library's pool threads hash the blocks, four at a time with AVX-512;
-//   device  the device(s) hash them over PCIe (the host pipeline; kernels reading the
-//           registered arena in place for a commit);
-//   split   both at once, on disjoint blocks of the one call: the host threads take pieces
-//           from the front, each device takes chunks from the back, each chunk sized so
-//           that the device finishes when everyone else does (SplitQueue), until they meet.
-// One engine runs the host and split legs (split_run; the host leg is a split without
-// devices). The routed entry points take the leg with the smallest predicted time, from
-// rates that start at priors measured on MI355X and that every call large
-// enough to time measures again (RouteModel).
+// The cost model, the rates, the split queue and the decision of a routed call are
+// route_plan.h; here are the facts it decides on and the legs it chooses among. One engine
+// runs the host and split legs (split_run; the host leg is a split without devices).
 namespace {
 
-// A host pass is split over threads only in pieces of at least this many bytes (~10 us of
-// hashing on one core, about what the pool's fork/join costs).
-constexpr uint64_t kHostMinBytesPerThread = 256 * 1024;
-constexpr double kHostLevelUs = 10.0;             // fork/join of a parallel pass
-constexpr double kDevCallUs = 10.0;               // device commit: a call
-constexpr double kDevLevelUs = 6.0;               // device commit: a launch per height
-constexpr double kDevChainBytesPerUs = 1600.0;    // one 4-lane XXH64 chain on gfx950 (32 KiB in ~20 us)
-constexpr double kDevBatchCallUs = 16.0;          // stage, launch, copy back and sync one small batch
-constexpr double kStageCopyBytesPerUs = 55000.0;  // pageable -> pinned staging copy (8 threads)
-constexpr double kSplitChunkUs = 8.0;             // a chunk issued behind one in flight: launch, copy back
-constexpr double kSplitMinClaimBytes = 1 << 20;   // a smaller device claim costs about what it saves
-constexpr double kSplitDmaBytes = 32 << 20;       // strided claims from this size take the copy engine
-constexpr double kSplitGain = 0.95;               // the split is taken only when predicted 5% faster
-constexpr double kSplitGainCached = 0.8;          // ... 20% for a call of at most kHostCacheBytes
-constexpr double kHostOnlyUs = 10.0;              // calls one host thread finishes this fast are not planned
-constexpr double kSplitMinSaveUs = 30.0;          // ... and only when it saves at least this much
-
-// Priors, bytes/us: the rates measured on an MI355X box with its EPYC 9575F host
-// (profiles/r04_batch_e2e/, r04_commit_e2e/).
-constexpr double kPriorHostThreadX4 = 48000.0;  // one thread hashing four blocks at once (AVX-512)
-constexpr double kPriorHostThread = 24000.0;    // one thread, scalar XXH64 (no AVX-512)
-constexpr double kPriorHostMemory = 180000.0;   // the pool: host memory bound (the slower box, 179 GB/s)
-constexpr double kPriorLinkPinned = 55000.0;    // the device pipeline from pinned / registered memory
-constexpr double kPriorLinkPageable = 55000.0;  // the same through pinned staging, copy overlapped
-constexpr double kPriorLinkInplace = 50000.0;   // kernels reading registered memory in place (49-55 GB/s)
-constexpr double kPriorDeviceLatencyUs = 150.0; // a split's device part until its first chunk is back
-                                                // (profiles/r05_first/: c5-size splits ~150 us over the host)
-constexpr double kLearnWeight = 0.25;           // EWMA weight of one call's observed rate
-constexpr uint64_t kLearnMinHostBytes = 8ULL << 20;   // below: fork/join noise
-constexpr uint64_t kLearnMinLinkBytes = 64ULL << 20;  // below: launch and sync noise
-// A host pass of at most this many bytes can run from the host's caches (a storm commit,
-// ~38 MB, written by the caller just before): the pool's cap on it is learned apart from
-// the cap on passes that stream from DRAM (c5 on the pool: ~100 us = 380 GB/s, against
-// 180-330 GB/s for an 8 GiB batch, profiles/r05_third/).
-constexpr uint64_t kHostCacheBytes = 64ULL << 20;
-
-enum class Link { kPinned, kPageable, kInplace };
-
-class RouteModel {
-  public:
-    static RouteModel& get() {
-        static RouteModel m;
-        return m;
-    }
-    stormck_route_rates now() {
-        std::lock_guard<std::mutex> g(mu_);
-        return r_;
-    }
-    // host_thread alone, without the lock: what a routed call's host-only test reads
-    double host_thread() const { return ht_.load(std::memory_order_relaxed); }
-    void set(const stormck_route_rates* r, bool freeze) {
-        std::lock_guard<std::mutex> g(mu_);
-        r_ = r ? *r : priors();
-        r_.observations = 0;
-        frozen_ = freeze;
-        ht_.store(r_.host_thread, std::memory_order_relaxed);
-    }
-    // A host pass: `bytes` hashed on `threads` threads in `us`. One thread measures the
-    // per-thread rate; a pool pass either the threads (it ran at their rate) or the cap
-    // that host memory and shared cores put on them (it ran below it).
-    void learn_host(uint64_t bytes, unsigned threads, double us) {
-        if (bytes < kLearnMinHostBytes || us <= 0) return;
-        // the plans add the fork/join of a spread pass on top of bytes / rate: learn the
-        // rate without it
-        const double rate = static_cast<double>(bytes) / std::max(1.0, us - (threads > 1 ? kHostLevelUs : 0.0));
-        std::lock_guard<std::mutex> g(mu_);
-        if (frozen_) return;
-        double& cap = bytes <= kHostCacheBytes ? r_.host_cached : r_.host_memory;
-        if (threads <= 1) {
-            r_.host_thread = ewma(r_.host_thread, rate);
-        } else if (rate >= 0.8 * threads * r_.host_thread) {
-            r_.host_thread = ewma(r_.host_thread, rate / threads);
-            cap = std::max(cap, rate);
-        } else {
-            cap = ewma(cap, rate);
-        }
-        ht_.store(r_.host_thread, std::memory_order_relaxed);
-        ++r_.observations;
-    }
-    // One device's transfer: `bytes` in `us` beyond the call's fixed latency.
-    void learn_link(Link k, uint64_t bytes, double us) {
-        if (bytes < kLearnMinLinkBytes || us <= 0) return;
-        const double rate = static_cast<double>(bytes) / us;
-        std::lock_guard<std::mutex> g(mu_);
-        if (frozen_) return;
-        double& r = k == Link::kPinned ? r_.link_pinned : (k == Link::kPageable ? r_.link_pageable : r_.link_inplace);
-        r = ewma(r, rate);
-        ++r_.observations;
-    }
-    // A split's device part: its first chunk came back `us` after the call posted it, of
-    // which `bytes` over the link at the current rate account for `bytes / rate`.
-    // One observation moves the latency up by at most a quarter of itself (plus 25 us): a
-    // spike (the device's first kernel launches in a process loading their code, tens of
-    // ms) would otherwise price the devices out of every later split, and a device that
-    // never gets a chunk is never measured again to correct it.
-    void learn_latency(uint64_t bytes, double rate, double us) {
-        if (us <= 0 || rate <= 0) return;
-        std::lock_guard<std::mutex> g(mu_);
-        if (frozen_) return;
-        const double lat = std::min(std::max(1.0, us - static_cast<double>(bytes) / rate),
-                                    2.0 * r_.device_latency + 100.0);
-        r_.device_latency = ewma(r_.device_latency, lat);
-        ++r_.observations;
-    }
-
-  private:
-    RouteModel() : r_(priors()), ht_(r_.host_thread) {}
-    static stormck_route_rates priors() {
-        stormck_route_rates r;
-        std::memset(&r, 0, sizeof r);
-        r.host_thread = host::has_x4() ? kPriorHostThreadX4 : kPriorHostThread;
-        r.host_memory = kPriorHostMemory;
-        r.host_cached = kPriorHostMemory;
-        r.link_pinned = kPriorLinkPinned;
-        r.link_pageable = kPriorLinkPageable;
-        r.link_inplace = kPriorLinkInplace;
-        r.device_latency = kPriorDeviceLatencyUs;
-        return r;
-    }
-    static double ewma(double old, double obs) { return old + kLearnWeight * (obs - old); }
-    std::mutex mu_;
-    stormck_route_rates r_;
-    std::atomic<double> ht_;
-    bool frozen_ = false;
-};
-
-// Aggregate rate of `threads` host threads.
-double host_rate(const stormck_route_rates& r, unsigned threads, uint64_t bytes) {
-    const double cap = bytes <= kHostCacheBytes ? r.host_cached : r.host_memory;
-    return threads <= 1 ? r.host_thread : std::min(threads * r.host_thread, cap);
-}
-
-// Host threads a split may use beside `nd` device workers: the pool, less one CPU per
-// device where the pool alone would take every CPU the process may use. A device's worker
-// and the HIP runtime threads serving it need a CPU now and then; on a GPU box, whose
-// process gets 16 CPUs by quota, 16 hashing threads beside them starved them, and c5-size
-// splits lost 20-30 % (profiles/r05_seventh/).
-unsigned split_threads(ForkJoin& fj, unsigned nd) {
-    if (nd == 0) return fj.size();
-    return fj.size() + nd > fj.cpus() ? std::max(1u, fj.cpus() > nd ? fj.cpus() - nd : 1u) : fj.size();
-}
-
-// Threads a host pass of `bytes` uses out of `nt` allowed.
-unsigned host_threads_for(uint64_t bytes, unsigned nt) {
-    return static_cast<unsigned>(std::min<uint64_t>(std::max(1u, nt), std::max<uint64_t>(1, bytes / kHostMinBytesPerThread)));
+// The one model of the process.
+RouteModel& route_model() {
+    static RouteModel m(host::has_x4());
+    return m;
 }
 
 double now_us() {
@@ -2256,20 +2118,6 @@ int route_devices(std::vector<int>* out) {
 // The devices a split may use: the caller's list, each device once, or the route devices.
 int split_devices(const int* devices, int n_devices, std::vector<int>* out) {
     return (devices || n_devices) ? check_devices(devices, n_devices, true, out) : route_devices(out);
-}
-
-// Threads the host part of a routed call may use: host_threads (0 = the pool). While another
-// call holds the pool, waiting for it pays only when the predicted wait plus this call's
-// time on the pool beats this call on its own thread (a small call behind a large one runs
-// at once on its caller's thread; a large one queues behind it). time_with(t): the call's
-// predicted time with t threads.
-template <class TimeWith>
-unsigned routed_threads(uint32_t host_threads, TimeWith&& time_with) {
-    const unsigned nt = pool_threads(host_threads);
-    if (nt <= 1) return 1;
-    const double busy = ForkJoin::get().busy_for_us();
-    if (busy <= 0) return nt;
-    return busy + time_with(nt) < time_with(1) ? nt : 1;
 }
 
 // One persistent host thread per device drives that device's part of a split (a thread per
@@ -2363,56 +2211,6 @@ void hash_blocks(const Blocks& B, uint64_t a, uint64_t b, Take&& take) {
     }
     for (; i < b; ++i) take(i, host::xxh64(B.at(i), B.len_of(i)));
 }
-
-// The blocks of one call, shared by its host threads (from the front) and its devices
-// (from the back). Balanced: a device claims b bytes so that, with I bytes in flight and
-// rate r_d, it finishes no later than the host threads and the other devices (rate r_o)
-// finish the R bytes nobody has claimed:
-//     L + (I + b) / r_d = (R - b) / r_o   ->   b = (R / r_o - L - I / r_d) / (1 / r_d + 1 / r_o)
-// (L: the chunk's latency); a claim below kSplitMinClaimBytes ends the device's part.
-// Fixed: the devices own exactly the last `fixed` blocks, the host threads the others.
-class SplitQueue {
-  public:
-    SplitQueue(uint64_t n, uint64_t fixed, double bytes_per_block, double r_host, double r_dev, unsigned ndev)
-        : lo_(0), hi_(n), split_(fixed == STORMCK_SPLIT_BALANCED ? UINT64_MAX : n - std::min(fixed, n)),
-          bpb_(bytes_per_block), r_host_(r_host), r_dev_(r_dev), ndev_(ndev) {}
-    bool host(uint64_t piece, uint64_t* a, uint64_t* b) {
-        std::lock_guard<std::mutex> g(mu_);
-        const uint64_t end = split_ != UINT64_MAX ? split_ : hi_;
-        if (lo_ >= end) return false;
-        *a = lo_;
-        *b = std::min(end, lo_ + piece);
-        lo_ = *b;
-        return true;
-    }
-    bool device(double inflight, double lat_us, uint64_t max_blocks, uint64_t* a, uint64_t* b) {
-        std::lock_guard<std::mutex> g(mu_);
-        uint64_t cnt = 0;
-        if (split_ != UINT64_MAX) {
-            if (hi_ <= split_) return false;
-            cnt = std::min(max_blocks, hi_ - split_);
-        } else {
-            if (hi_ <= lo_) return false;
-            const uint64_t avail = hi_ - lo_;
-            const double R = static_cast<double>(avail) * bpb_;
-            const double r_o = r_host_ + (std::max(ndev_, 1u) - 1) * r_dev_;
-            const double want = r_o <= 0 ? R : (R / r_o - lat_us - inflight / r_dev_) / (1.0 / r_dev_ + 1.0 / r_o);
-            if (want < kSplitMinClaimBytes) return false;
-            cnt = std::min<uint64_t>({static_cast<uint64_t>(want / bpb_), max_blocks, avail});
-            if (cnt == 0) return false;
-        }
-        *a = hi_ - cnt;
-        *b = hi_;
-        hi_ -= cnt;
-        return true;
-    }
-
-  private:
-    std::mutex mu_;
-    uint64_t lo_, hi_, split_;
-    double bpb_, r_host_, r_dev_;
-    unsigned ndev_;
-};
 
 struct SplitArgs {
     Blocks B;
@@ -2561,10 +2359,10 @@ int split_run(SplitArgs& A, const std::vector<int>& devs, unsigned pl, uint64_t 
     const uint64_t bytes = B.bytes(0, n);
     const double bpb = std::max(1.0, static_cast<double>(bytes) / static_cast<double>(n));
     A.bytes_per_block = bpb;
-    const stormck_route_rates rt = RouteModel::get().now();
+    const stormck_route_rates rt = route_model().now();
     ForkJoin& fj = ForkJoin::get();
     const unsigned nd = static_cast<unsigned>(devs.size());
-    pl = std::max(1u, std::min(pl, split_threads(fj, nd)));
+    pl = std::max(1u, std::min(pl, split_threads(fj.size(), fj.cpus(), nd)));
     const double r_dev = A.in_place ? rt.link_inplace : rt.link_pinned;
     const double r_host = host_rate(rt, pl, bytes);
     const double lat = rt.device_latency;
@@ -2648,7 +2446,7 @@ int split_run(SplitArgs& A, const std::vector<int>& devs, unsigned pl, uint64_t 
                                       " blocks left unhashed");
     R->first_bad = fb;
     R->n_bad = nb;
-    RouteModel& m = RouteModel::get();
+    RouteModel& m = route_model();
     // host rates from host legs only: in a split the host threads share host memory with
     // the devices' reads (and leave them a CPU), so their rate there is not the host leg's
     // the plans compare against (c5's learned cap fell 25 % under the measured host leg
@@ -2683,117 +2481,6 @@ int split_run(SplitArgs& A, const std::vector<int>& devs, unsigned pl, uint64_t 
                      h0 + h_us - t_post, t_end - t_post, d.c_str());
     }
     return STORMCK_OK;
-}
-
-// ---- the batch cost model ----------------------------------------------------------
-struct LegPlan {
-    uint32_t leg = STORMCK_LEG_HOST;
-    double us[3] = {0, INFINITY, INFINITY};  // host, device, split
-    double best() const { return us[leg == STORMCK_LEG_DEVICE ? 1 : (leg == STORMCK_LEG_SPLIT ? 2 : 0)]; }
-};
-
-// The split is taken only when it is predicted to save both kSplitGain of the best single
-// leg and kSplitMinSaveUs: on small calls the devices' part is a few chunks whose start and
-// finish vary by tens of microseconds (profiles/r05_fourth/), more than it could save. A
-// call of at most kHostCacheBytes needs kSplitGainCached: its host leg runs twice as fast
-// from warm host caches as from cold ones (c5 on the pool: 77 us called back to back,
-// 135-170 us between other work, profiles/r05_learn/), so its learned rate is a blend and
-// the prediction loose, and the device's part gains nothing from the caches. Measured on six
-// boxes, the split never beat the pool by more than 6% at c5 size, and beat one host
-// thread by 1.6-2x.
-void pick_leg(LegPlan* p, double bytes) {
-    double best = p->us[0];
-    p->leg = STORMCK_LEG_HOST;
-    if (p->us[1] < best) {
-        best = p->us[1];
-        p->leg = STORMCK_LEG_DEVICE;
-    }
-    const double gain = bytes <= static_cast<double>(kHostCacheBytes) ? kSplitGainCached : kSplitGain;
-    if (p->us[2] < gain * best && p->us[2] < best - kSplitMinSaveUs) p->leg = STORMCK_LEG_SPLIT;
-}
-
-// Time of a split that hashes `bytes` on host threads at r_h and devices at r_d together,
-// or INFINITY if it beats the host alone (host_us) by nothing.
-double split_us(double bytes, double r_h, double r_d, double lat, double overhead, double host_us) {
-    const double t = (bytes + r_d * lat) / (r_h + r_d) + overhead;
-    return t < host_us ? t : INFINITY;
-}
-
-// The three legs of a host-memory batch: the host threads; the device pipeline (a call, one
-// chain over the longest block, the bytes over ndev links, and for pageable memory the first
-// chunk's staging copy, which nothing overlaps); the split (pinned memory only: from
-// pageable memory the devices need host threads to copy, which hash faster than they copy),
-// the devices reading in place after their start latency.
-// A call one host thread finishes faster than any device can start returning (kHostOnlyUs: a
-// device's start latency is tens of microseconds) is not planned: the routed call takes the
-// host leg on its own thread at once, paying no planning, no device list and no pool
-// (storm's smallest commits, every revision: the singularity, cache/cache.go:64-85).
-bool host_only(double host_thread, double bytes) { return bytes / host_thread < kHostOnlyUs; }
-bool host_only(const stormck_route_rates& r, double bytes) { return host_only(r.host_thread, bytes); }
-
-LegPlan host_only_plan(const stormck_route_rates& r, double bytes) {
-    LegPlan p;
-    p.us[0] = bytes / r.host_thread;
-    return p;
-}
-
-LegPlan plan_batch(const stormck_route_rates& r, uint64_t n, const HostBatch& s, bool pinned, bool staged_ok,
-                   unsigned nt, unsigned ndev) {
-    LegPlan p;
-    const unsigned pl = host_threads_for(s.bytes, nt);
-    const double bytes = static_cast<double>(s.bytes), chain = static_cast<double>(s.longest) / kDevChainBytesPerUs;
-    const double level = pl > 1 ? kHostLevelUs : 0.0;
-    const double r_h = host_rate(r, pl, s.bytes);
-    p.us[0] = bytes / r_h + level;
-    if (ndev && staged_ok) {
-        const double link = pinned ? r.link_pinned : r.link_pageable;
-        const double fill = pinned ? 0.0 : static_cast<double>(std::min<uint64_t>(s.bytes, kChunkBytes)) / kStageCopyBytesPerUs;
-        p.us[1] = kDevBatchCallUs + chain + bytes / (ndev * link) + fill;
-        if (pinned && n >= 2) {
-            const unsigned ps = std::min(pl, split_threads(ForkJoin::get(), ndev));
-            p.us[2] = split_us(bytes, host_rate(r, ps, s.bytes), ndev * r.link_inplace, r.device_latency,
-                               ps > 1 ? kHostLevelUs : 0.0, p.us[0]);
-        }
-    }
-    pick_leg(&p, bytes);
-    return p;
-}
-
-// ---- the commit cost model ----------------------------------------------------------
-// One height on the host threads: its bytes at the threads' rate, at least one block's
-// chain, and a fork/join when it is spread.
-double host_height_us(const stormck_route_rates& r, const CommitShape& s, size_t l, unsigned nt) {
-    const unsigned pl = host_threads_for(s.bytes[l], nt);
-    const double t = std::max(static_cast<double>(s.bytes[l]) / host_rate(r, pl, s.bytes[l]),
-                              static_cast<double>(s.longest[l]) / r.host_thread);
-    return t + (pl > 1 ? kHostLevelUs : 0.0);
-}
-
-// The three legs of a commit: the host threads, height by height; the device in place over
-// the link (a call, then per height a launch and the longer of one chain over its longest
-// block and its bytes over the link); the split (height 0, the leaves, on both; the upper
-// heights on the host). The device legs need a registered arena.
-LegPlan plan_commit(const stormck_route_rates& r, const CommitShape& s, bool registered, unsigned nt, unsigned ndev) {
-    LegPlan p;
-    p.us[0] = 0;
-    for (size_t l = 0; l < s.cnt.size(); ++l) p.us[0] += host_height_us(r, s, l, nt);
-    if (registered && ndev && !s.cnt.empty()) {
-        p.us[1] = kDevCallUs;
-        for (size_t l = 0; l < s.cnt.size(); ++l)
-            p.us[1] += kDevLevelUs + std::max(static_cast<double>(s.longest[l]) / kDevChainBytesPerUs,
-                                              static_cast<double>(s.bytes[l]) / r.link_inplace);
-        if (s.cnt[0] >= 2) {
-            const double h0 = host_height_us(r, s, 0, nt);
-            const unsigned pl = std::min(host_threads_for(s.bytes[0], nt), split_threads(ForkJoin::get(), ndev));
-            const double t0 = split_us(static_cast<double>(s.bytes[0]), host_rate(r, pl, s.bytes[0]), ndev * r.link_inplace,
-                                       r.device_latency, pl > 1 ? kHostLevelUs : 0.0, h0);
-            p.us[2] = p.us[0] - h0 + t0;
-        }
-    }
-    double total = 0;
-    for (uint64_t b : s.bytes) total += static_cast<double>(b);
-    pick_leg(&p, total);
-    return p;
 }
 
 // ---- f1 on the host threads: the plan and the heights ---------------------------------
@@ -2939,9 +2626,10 @@ int batch_routed(const void* base, uint64_t stride, const uint32_t* lens, uint32
     if (rc) return rc;
     if (n == 0) return empty_batch(first_bad, n_bad);
     // a batch that one host thread hashes faster than any device can start returning takes
-    // the host leg without planning (host_only); it only needs the range to be readable host
-    // memory (registered, or readable: what the host leg alone checks), not its kind
-    if (host_only(RouteModel::get().host_thread(), static_cast<double>(hb.bytes))) {
+    // the host leg without planning (host_only), before any fact the decision below needs is
+    // gathered; it only needs the range to be readable host memory (registered, or readable:
+    // what the host leg alone checks), not its kind
+    if (host_only(route_model().host_thread(), hb.bytes)) {
         if (!in_registered(base, hb.extent) && !host_readable(base, hb.extent))
             return not_host_memory(classify(base, hb.extent));
         if (leg_used) *leg_used = STORMCK_LEG_HOST;
@@ -2949,18 +2637,16 @@ int batch_routed(const void* base, uint64_t stride, const uint32_t* lens, uint32
     }
     const Mem mem = classify(base, hb.extent);
     if (mem == Mem::kDevice || mem == Mem::kUnreadable) return not_host_memory(mem);
-    const stormck_route_rates rt = RouteModel::get().now();
+    const stormck_route_rates rt = route_model().now();
     std::vector<int> devs;
     rc = route_devices(&devs);
     if (rc) return rc;
     const bool pinned = mem != Mem::kPageable;
-    auto plan_for = [&](unsigned t) {  // the device pipeline stages whole blocks through 256 MiB chunks
-        return plan_batch(rt, n, hb, pinned, hb.step <= kChunkBytes, t, static_cast<unsigned>(devs.size()));
-    };
-    const unsigned nt = routed_threads(host_threads, [&](unsigned t) { return plan_for(t).best(); });
-    const LegPlan p = plan_for(nt);
-    if (leg_used) *leg_used = p.leg;
-    if (p.leg == STORMCK_LEG_DEVICE) {
+    // the device pipeline stages whole blocks through 256 MiB chunks
+    const Route route = route_batch(rt, n, hb.bytes, hb.longest, pinned, hb.step <= kChunkBytes,
+                                    static_cast<unsigned>(devs.size()), pool_facts(host_threads, true));
+    if (leg_used) *leg_used = route.plan.leg;
+    if (route.plan.leg == STORMCK_LEG_DEVICE) {
         const double t0 = now_us();
         int cur = 0;
         HIP_TRY(hipGetDevice(&cur));
@@ -2969,13 +2655,13 @@ int batch_routed(const void* base, uint64_t stride, const uint32_t* lens, uint32
                  : host_pipeline_multi(base, stride, lens, len, n, out, expected, first_bad, n_bad, devs.data(),
                                        static_cast<int>(devs.size()));
         if (rc == STORMCK_OK)
-            RouteModel::get().learn_link(pinned ? Link::kPinned : Link::kPageable, hb.bytes / devs.size(),
-                                         now_us() - t0 - kDevBatchCallUs -
-                                             static_cast<double>(hb.longest) / kDevChainBytesPerUs);
+            route_model().learn_link(pinned ? Link::kPinned : Link::kPageable, hb.bytes / devs.size(),
+                                     now_us() - t0 - kDevBatchCallUs -
+                                         static_cast<double>(hb.longest) / kDevChainBytesPerUs);
         return rc;
     }
-    const unsigned pl = host_threads_for(hb.bytes, nt);
-    if (p.leg == STORMCK_LEG_SPLIT)
+    const unsigned pl = host_threads_for(hb.bytes, route.threads);
+    if (route.plan.leg == STORMCK_LEG_SPLIT)
         return batch_legs(hb, out, expected, first_bad, n_bad, devs, pl, STORMCK_SPLIT_BALANCED, nullptr,
                           mem == Mem::kMapped);
     return batch_host_leg(hb, out, expected, first_bad, n_bad, pl);
@@ -3073,23 +2759,15 @@ int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_
     if (mem == Mem::kUnreadable) return not_host_memory(mem);
     const bool registered = mem == Mem::kMapped;
     // a forest one host thread hashes faster than any device can start returning (storm's
-    // smallest commits: a few blocks) takes the host leg without planning (host_only)
-    {
-        // host_only(total) as a byte bound, so the sum stops at the bound without a division
-        // per block (a 111-block `-tags test` forest paid 0.1 us for them)
-        const double bound = kHostOnlyUs * RouteModel::get().host_thread();
-        uint64_t total = 0;
-        for (uint64_t i = 0; i < n && static_cast<double>(total) < bound; ++i) total += blocks[i].length;
-        if (static_cast<double>(total) < bound) {
-            if (leg_used) *leg_used = STORMCK_LEG_HOST;
-            if (registered) {
-                rc = stream_drained(static_cast<hipStream_t>(stream));
-                if (rc) return rc;
-            }
-            return stormck_commit_host(arena, blocks, n, revision, last_allocated_block, out_checksums, 1);
-        }
+    // smallest commits: a few blocks) takes the host leg without planning (host_only), before
+    // the forest is walked
+    if (host_only(route_model().host_thread(), blocks, n)) {
+        if (leg_used) *leg_used = STORMCK_LEG_HOST;
+        rc = registered ? stream_drained(static_cast<hipStream_t>(stream)) : STORMCK_OK;
+        if (rc) return rc;
+        return stormck_commit_host(arena, blocks, n, revision, last_allocated_block, out_checksums, 1);
     }
-    const stormck_route_rates rt = RouteModel::get().now();
+    const stormck_route_rates rt = route_model().now();
     std::vector<int> devs;
     rc = route_devices(&devs);
     if (rc) return rc;
@@ -3100,13 +2778,10 @@ int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_
     if (rc) return rc;
     CommitShape shape;
     commit_shape(H, blocks, n, &shape);
-    auto plan_for = [&](unsigned t) {
-        return plan_commit(rt, shape, registered, t, static_cast<unsigned>(devs.size()));
-    };
-    const unsigned nt = routed_threads(host_threads, [&](unsigned t) { return plan_for(t).best(); });
-    const LegPlan p = plan_for(nt);
-    if (leg_used) *leg_used = p.leg;
-    if (p.leg == STORMCK_LEG_DEVICE) {
+    const Route route =
+        route_commit(rt, shape, registered, static_cast<unsigned>(devs.size()), pool_facts(host_threads, true));
+    if (leg_used) *leg_used = route.plan.leg;
+    if (route.plan.leg == STORMCK_LEG_DEVICE) {
         void* d_arena = nullptr;  // the kernels read and write the registered arena in place
         HIP_TRY(hipHostGetDevicePointer(&d_arena, arena, 0));
         PhaseTimer pt("commit");  // the heights are walked already
@@ -3114,12 +2789,11 @@ int stormck_commit(void* arena, stormck_dirty_block* blocks, uint64_t n, uint64_
     }
     // host threads read the arena now: device work the caller queued on `stream` (e.g. a
     // kernel writing blocks into the registered arena) must have landed first
-    if (registered) {
-        rc = stream_drained(static_cast<hipStream_t>(stream));
-        if (rc) return rc;
-    }
-    return commit_host_run(static_cast<uint8_t*>(arena), blocks, H, revision, last_allocated_block, out_checksums, nt,
-                           p.leg == STORMCK_LEG_SPLIT ? devs : std::vector<int>{}, STORMCK_SPLIT_BALANCED, nullptr);
+    rc = registered ? stream_drained(static_cast<hipStream_t>(stream)) : STORMCK_OK;
+    if (rc) return rc;
+    if (route.plan.leg != STORMCK_LEG_SPLIT) devs.clear();
+    return commit_host_run(static_cast<uint8_t*>(arena), blocks, H, revision, last_allocated_block, out_checksums,
+                           route.threads, devs, STORMCK_SPLIT_BALANCED, nullptr);
 }
 
 // ---- host-memory batches ---------------------------------------------------------------
@@ -3169,7 +2843,7 @@ int stormck_verify_split(const void* base, uint64_t stride, const uint32_t* lens
 // ---- the route model, for callers and tests --------------------------------------------
 int stormck_route_get_rates(stormck_route_rates* rates) {
     if (!rates) return fail(STORMCK_EINVAL, "rates is null");
-    *rates = RouteModel::get().now();
+    *rates = route_model().now();
     return STORMCK_OK;
 }
 
@@ -3178,7 +2852,7 @@ int stormck_route_set_rates(const stormck_route_rates* rates, uint32_t flags) {
     if (rates && !(rates->host_thread > 0 && rates->host_memory > 0 && rates->host_cached > 0 && rates->link_pinned > 0 &&
                    rates->link_pageable > 0 && rates->link_inplace > 0 && rates->device_latency >= 0))
         return fail(STORMCK_EINVAL, "every rate must be positive (and the latency not negative)");
-    RouteModel::get().set(rates, (flags & STORMCK_RATES_FREEZE) != 0);
+    route_model().set(rates, (flags & STORMCK_RATES_FREEZE) != 0);
     return STORMCK_OK;
 }
 
@@ -3204,11 +2878,8 @@ int stormck_route_plan_batch(uint64_t stride, const uint32_t* lens, uint32_t len
     HostBatch s;
     const int rc = measure_batch(stride, lens, len, n, &s);
     if (rc) return rc;
-    const stormck_route_rates rt = RouteModel::get().now();
-    const LegPlan p = host_only(rt, static_cast<double>(s.bytes))
-                          ? host_only_plan(rt, static_cast<double>(s.bytes))
-                          : plan_batch(rt, n, s, memory == STORMCK_MEM_PINNED, s.step <= kChunkBytes,
-                                       pool_threads(host_threads), n_devices);
+    const LegPlan p = route_batch(route_model().now(), n, s.bytes, s.longest, memory == STORMCK_MEM_PINNED,
+                                  s.step <= kChunkBytes, n_devices, pool_facts(host_threads, false)).plan;
     *leg = n ? p.leg : STORMCK_LEG_NONE;
     if (predicted_us) std::memcpy(predicted_us, p.us, sizeof p.us);
     return STORMCK_OK;
@@ -3219,17 +2890,13 @@ int stormck_route_plan_commit(const stormck_dirty_block* blocks, uint64_t n, uin
     if (!leg) return fail(STORMCK_EINVAL, "leg is null");
     if (memory > STORMCK_MEM_PINNED) return fail(STORMCK_EINVAL, "unknown memory kind");
     if (n > 0 && !blocks) return fail(STORMCK_EINVAL, "blocks is null");
-    const unsigned nt = pool_threads(host_threads);
     Heights H;
     if (commit_heights(blocks, n, 0, plan_par(host_threads), &H) != CommitError::Ok)
         return fail(STORMCK_EINVAL, "malformed forest (parent range or cycle)");
     CommitShape shape;
     commit_shape(H, blocks, n, &shape);
-    const stormck_route_rates rt = RouteModel::get().now();
-    double total = 0;
-    for (uint64_t b : shape.bytes) total += static_cast<double>(b);
-    const LegPlan p = host_only(rt, total) ? host_only_plan(rt, total)
-                                           : plan_commit(rt, shape, memory == STORMCK_MEM_PINNED, nt, n_devices);
+    const LegPlan p = route_commit(route_model().now(), shape, memory == STORMCK_MEM_PINNED, n_devices,
+                                   pool_facts(host_threads, false)).plan;
     *leg = n ? p.leg : STORMCK_LEG_NONE;
     if (predicted_us) std::memcpy(predicted_us, p.us, sizeof p.us);
     return STORMCK_OK;

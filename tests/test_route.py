@@ -20,7 +20,7 @@ from storm_amd import commit as sc
 
 RATES = dict(host_thread=40000.0, host_memory=180000.0, host_cached=180000.0, link_pinned=55000.0,
              link_pageable=50000.0, link_inplace=52000.0, device_latency=120.0)
-LEVEL_US, CALL_US, CHAIN = 10.0, 16.0, 1600.0  # stormck.hip kHostLevelUs, kDevBatchCallUs, kDevChainBytesPerUs
+LEVEL_US, CALL_US, CHAIN = 10.0, 16.0, 1600.0  # route_plan.h kHostLevelUs, kDevBatchCallUs, kDevChainBytesPerUs
 POOL = 16
 GIB8 = 262144  # 8 GiB of 32 KiB blocks
 
@@ -58,7 +58,7 @@ def _pool():
 
 
 def _split_threads(k):
-    # host threads beside k device workers (stormck.hip split_threads)
+    # host threads beside k device workers (route_plan.h split_threads)
     pool, cpus = _pool(), _cpus()
     return pool if pool + k <= cpus else max(1, cpus - k if cpus > k else 1)
 
