@@ -331,6 +331,47 @@ inline ScrubResult ScrubTree(const void* store, const stormck_scrub_layout& layo
                                                           reachable, &report, stream), report);
 }
 
+// Trace (stormck_trace_device / stormck_trace_host): cache.TraceTagForReading for n tags at
+// once through the tree at `root`, every block on the way verified against the checksum its
+// parent holds. results gets one stormck_trace_result per tag and leaf_checksums (optional)
+// the checksum the parent holds per FOUND tag. `device` = true: store, tags, results and
+// leaf_checksums are device memory and the trace is queued on `stream`; false: host memory on
+// host_threads pool threads (0 = the pool). A damaged tree is not an exception: the statuses
+// and the report say what is wrong, and TraceResult::message is the text of the first bad tag's
+// error. flags: STORMCK_TRACE_LEAVES_UNVERIFIED.
+struct TraceResult {
+    stormck_trace_report report;
+    std::string message;  // "" when no tag ended MISMATCH, RANGE, TYPE or DEPTH
+    bool ok(uint64_t n) const { return report.first_bad >= n; }
+};
+inline TraceResult TraceTags(const void* store, const stormck_scrub_layout& layout, const Pointer& root,
+                             BlockType root_type, uint32_t leaf_kind, uint32_t leaf_len, const uint64_t* tags, uint64_t n,
+                             stormck_trace_result* results, bool device, uint32_t flags = 0,
+                             uint64_t* leaf_checksums = nullptr, void* stream = nullptr, uint32_t host_threads = 0) {
+    stormck_trace_report report{};
+    const stormck_pointer* r = reinterpret_cast<const stormck_pointer*>(&root);
+    int rc;
+    if (!device) {
+        rc = stormck_trace_host(store, &layout, r, root_type, leaf_kind, leaf_len, tags, n, flags, results, leaf_checksums,
+                                &report, host_threads);
+    } else {
+        struct Workspace {
+            void* p = nullptr;
+            uint64_t bytes;
+            explicit Workspace(uint64_t n_tags) : bytes(stormck_trace_workspace_bytes(n_tags)) {
+                detail::check(stormck_device_alloc(bytes, &p));
+            }
+            ~Workspace() { (void)stormck_device_free(p); }
+            Workspace(const Workspace&) = delete;
+            Workspace& operator=(const Workspace&) = delete;
+        } ws(n);
+        rc = stormck_trace_device(store, &layout, r, root_type, leaf_kind, leaf_len, tags, n, flags, results,
+                                  leaf_checksums, ws.p, ws.bytes, &report, stream);
+    }
+    if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) throw DeviceError(rc);
+    return TraceResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
+}
+
 // ---- block layouts -------------------------------------------------------------
 
 // pointer.Block (blocks/pointer/block.go:10-13); PointersPerBlock = 1200 (params.go:6),

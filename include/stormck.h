@@ -569,6 +569,92 @@ int stormck_scrub_tree_host(const void* store, const stormck_scrub_layout* layou
                             uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, uint32_t* reachable,
                             stormck_scrub_report* report, uint32_t host_threads);
 
+/* ---- trace: storm's read path for many tags at once ----------------------------
+ * cache.TraceTagForReading (cache/trace.go:10-42) walks from a BlockOrigin down the pointer
+ * blocks, taking index = reminder % PointersPerBlock and reminder /= PointersPerBlock per
+ * level, and fetchBlock verifies every block on the way against the checksum its parent
+ * holds. This is that walk for n tags at once, level by level: one hash batch per tree level
+ * instead of one block per key per level. One tree is traced from an explicit root, as
+ * stormck_scrub_tree_* walks it: layout, root, root_type, leaf_kind and leaf_len mean what they
+ * mean there and take the same argument checks (a leaf is never expanded, whatever its kind).
+ *
+ * For tag t the walk starts at the root reference (parent 0, slot 0, depth 0, reminder t).
+ * A reference is handled by these rules, in this order:
+ *   ABSENT    the type byte is Free (storm returns exists == false)
+ *   TYPE      the type byte is above 2
+ *   RANGE     the address is 0 or >= n_blocks (tested before any multiplication; never read)
+ *   DEPTH     the reference is of Pointer type and 64 pointer blocks have already been verified
+ *             on this walk (a fanout of at least 2 leaves reminder 0 after 64 digits; storm
+ *             itself would spin on a cycle of verified blocks)
+ *   MISMATCH  the block, hashed over the pointer-block length or the leaf length, differs
+ *             from the checksum the reference holds
+ *   FOUND     the block is a verified leaf
+ * A verified pointer block at `address` continues the walk: depth += 1, slot = reminder %
+ * fanout, reminder /= fanout, and the next reference is entry `slot` of that block (parent =
+ * address). MISMATCH, RANGE and TYPE have the scrub's numbers.
+ *
+ * A block is hashed once per distinct reference (depth, parent, slot), however many tags pass
+ * through it; blocks_hashed counts exactly those references. */
+#define STORMCK_HAS_TRACE 1
+enum {
+    STORMCK_TRACE_FOUND = 0,
+    STORMCK_TRACE_MISMATCH = 1,
+    STORMCK_TRACE_RANGE = 2,
+    STORMCK_TRACE_TYPE = 3,
+    STORMCK_TRACE_ABSENT = 5,
+    STORMCK_TRACE_DEPTH = 6
+};
+/* A leaf reference ends FOUND without being hashed (after the TYPE and RANGE rules): for
+ * callers that read the leaf elsewhere, e.g. from a file with stormck_read_verify_fd against
+ * the checksum the parent holds, which d_leaf_checksums returns. */
+#define STORMCK_TRACE_LEAVES_UNVERIFIED 1u
+
+typedef struct stormck_trace_result {
+    uint64_t address;   /* the block the final reference names (as read, also when RANGE/TYPE); 0 for a Free root */
+    uint64_t reminder;  /* the tag reminder where the walk ended (storm's tagReminder for FOUND) */
+    uint64_t parent;    /* the block that holds the final reference, 0 = the caller's root */
+    uint32_t slot;      /* its slot there: together the BlockOrigin of the leaf or of the Free entry */
+    uint16_t depth;     /* pointer blocks verified on the way */
+    uint8_t status, reserved;
+} stormck_trace_result;
+
+typedef struct stormck_trace_report {
+    uint64_t n_status[7];       /* tags per STORMCK_TRACE_* status */
+    uint64_t blocks_hashed[2];  /* distinct references hashed: pointer blocks, leaves */
+    uint64_t bytes_hashed;
+    uint64_t first_bad;         /* the smallest tag index that ended MISMATCH, RANGE, TYPE or DEPTH; n if none */
+    uint32_t levels, reserved;  /* tree levels hashed */
+} stormck_trace_report;
+
+/* Bytes of device workspace a trace of n_tags needs: 256 + 12 * T + 118 * ((n_tags + 7) & ~7),
+ * T = the smallest power of two that is at least 64 and at least 2 * n_tags (the table of
+ * distinct references); at most 166 bytes per tag, whatever the image's size (DESIGN.md
+ * "Trace"). Host logic. */
+uint64_t stormck_trace_workspace_bytes(uint64_t n_tags);
+/* Trace the n tags at d_tags through the tree at `root` of the device-resident image d_store.
+ * d_results gets one result per tag, in the tags' order. d_leaf_checksums (optional, n u64):
+ * per FOUND tag the checksum its parent holds for the leaf, 0 for every other tag.
+ * Per level the distinct references are hashed by the batch dispatch
+ * (stormck_checksum_gather_device's), then k_trace_step ends or advances every live tag.
+ * Synchronous: queues its work on `stream` behind what is already there and returns when the
+ * results are in d_results and the report is filled. n == 0 is a no-op with a zero report;
+ * at most 2^31 tags per call. d_store, d_tags, d_results, d_leaf_checksums and d_workspace
+ * are 8-byte aligned. Returns STORMCK_EMISMATCH when first_bad < n, with the text of tag
+ * first_bad's error in stormck_last_error(); ABSENT is not an error. STORMCK_EINVAL for the
+ * scrub-tree argument errors, an unknown flag, a small workspace, misaligned pointers or a
+ * stream that is being captured. */
+int stormck_trace_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                         uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, const uint64_t* d_tags, uint64_t n,
+                         uint32_t flags, stormck_trace_result* d_results, uint64_t* d_leaf_checksums, void* d_workspace,
+                         uint64_t workspace_bytes, stormck_trace_report* report, void* stream);
+/* The same trace over an image in host memory with host pointers throughout, each level's
+ * distinct blocks hashed on host_threads library pool threads (0 = the pool). Same rules,
+ * results, report and return codes; needs no device and no workspace, and is not routed. */
+int stormck_trace_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                       uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, const uint64_t* tags, uint64_t n,
+                       uint32_t flags, stormck_trace_result* results, uint64_t* leaf_checksums,
+                       stormck_trace_report* report, uint32_t host_threads);
+
 /* ---- synthetic data (benchmarks / tests) -----------------------------------
  * Word w of block i = splitmix64(seed ^ (((first + i) << 20) + w)), w < stride/8,
  * little-endian. stride % 16 == 0, d_dst 16-byte aligned. */

@@ -90,6 +90,20 @@ class ScrubReportStruct(ctypes.Structure):
                 ("first_address", c_uint64), ("first_computed", c_uint64), ("first_expected", c_uint64)]
 
 
+class TraceResultStruct(ctypes.Structure):
+    """stormck_trace_result: where one tag's walk ended (32 bytes)."""
+
+    _fields_ = [("address", c_uint64), ("reminder", c_uint64), ("parent", c_uint64), ("slot", c_uint32),
+                ("depth", ctypes.c_uint16), ("status", c_uint8), ("reserved", c_uint8)]
+
+
+class TraceReportStruct(ctypes.Structure):
+    """stormck_trace_report."""
+
+    _fields_ = [("n_status", c_uint64 * 7), ("blocks_hashed", c_uint64 * 2), ("bytes_hashed", c_uint64),
+                ("first_bad", c_uint64), ("levels", c_uint32), ("reserved", c_uint32)]
+
+
 # name -> (restype, argtypes); mirrors include/stormck.h one to one.
 SIGNATURES = {
     "stormck_abi_version": (c_int, []),
@@ -171,6 +185,13 @@ SIGNATURES = {
     "stormck_scrub_tree_host": (
         c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_uint32, c_uint32, c_void_p,
                 POINTER(ScrubReportStruct), c_uint32]),
+    "stormck_trace_workspace_bytes": (c_uint64, [c_uint64]),
+    "stormck_trace_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_uint32, c_uint32, c_void_p,
+                c_uint64, c_uint32, c_void_p, c_void_p, c_void_p, c_uint64, POINTER(TraceReportStruct), c_void_p]),
+    "stormck_trace_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_uint32, c_uint32, c_void_p,
+                c_uint64, c_uint32, c_void_p, c_void_p, POINTER(TraceReportStruct), c_uint32]),
     "stormck_fill_synthetic_device": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p]),
 }
 

@@ -16,6 +16,7 @@
 #include <functional>
 #include <thread>
 #include <type_traits>
+#include <unordered_map>
 #include <vector>
 
 #include <dlfcn.h>
@@ -1260,6 +1261,7 @@ int host_pipeline_multi(const void* base, uint64_t stride, const uint32_t* lens,
 
 #include "multi_root.h"
 #include "scrub.h"
+#include "trace.h"
 
 }  // namespace
 
@@ -2925,6 +2927,24 @@ int stormck_scrub_tree_host(const void* store, const stormck_scrub_layout* layou
                             uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, uint32_t* reachable,
                             stormck_scrub_report* report, uint32_t host_threads) {
     return scrub_tree_host(store, layout, root, root_type, leaf_kind, leaf_len, reachable, report, host_threads);
+}
+
+uint64_t stormck_trace_workspace_bytes(uint64_t n_tags) { return trace_workspace_bytes(n_tags); }
+
+int stormck_trace_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                         uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, const uint64_t* d_tags, uint64_t n,
+                         uint32_t flags, stormck_trace_result* d_results, uint64_t* d_leaf_checksums, void* d_workspace,
+                         uint64_t workspace_bytes, stormck_trace_report* report, void* stream) {
+    return trace_device(d_store, layout, root, root_type, leaf_kind, leaf_len, d_tags, n, flags, d_results,
+                        d_leaf_checksums, d_workspace, workspace_bytes, report, stream);
+}
+
+int stormck_trace_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                       uint8_t root_type, uint32_t leaf_kind, uint32_t leaf_len, const uint64_t* tags, uint64_t n,
+                       uint32_t flags, stormck_trace_result* results, uint64_t* leaf_checksums,
+                       stormck_trace_report* report, uint32_t host_threads) {
+    return trace_host(store, layout, root, root_type, leaf_kind, leaf_len, tags, n, flags, results, leaf_checksums,
+                      report, host_threads);
 }
 
 int stormck_fill_synthetic_device(void* d_dst, uint64_t stride, uint64_t n, uint64_t first, uint64_t seed,
