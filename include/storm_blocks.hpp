@@ -372,6 +372,50 @@ inline TraceResult TraceTags(const void* store, const stormck_scrub_layout& layo
     return TraceResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
 }
 
+// Lookup (stormck_lookup_device / stormck_lookup_host): keystore.GetObjectID for n keys at once
+// in the key tree at `root`: the key tags, the trace above and the open-addressing probe of each
+// key's objectlist leaf. Key i is keys + (offsets ? offsets[i] : i * stride), (lens ? lens[i] :
+// len) bytes; results gets one stormck_lookup_result per key. addressing_offsets is
+// objectlist.AddressingOffsets (always a host array, chunks_per_block entries): the library
+// ships no table. `device` = true: store, keys, offsets, lens and results are device memory and
+// the lookup is queued on `stream`; false: host memory on host_threads pool threads. A damaged
+// tree or a key of a length storm refuses is not an exception: the statuses and the report say
+// what is wrong, and LookupResult::message is the text of the first bad key's error.
+struct LookupResult {
+    stormck_lookup_report report;
+    std::string message;  // "" when no key ended MISMATCH, RANGE, TYPE, DEPTH or KEY
+    bool ok(uint64_t n) const { return report.first_bad >= n; }
+};
+inline LookupResult GetObjectIDs(const void* store, const stormck_scrub_layout& layout, const Pointer& root,
+                                 BlockType root_type, const uint16_t* addressing_offsets, uint32_t chunks_per_block,
+                                 const void* keys, uint64_t stride, const uint64_t* offsets, const uint32_t* lens,
+                                 uint32_t len, uint64_t n, stormck_lookup_result* results, bool device, uint32_t flags = 0,
+                                 void* stream = nullptr, uint32_t host_threads = 0) {
+    stormck_lookup_report report{};
+    const stormck_pointer* r = reinterpret_cast<const stormck_pointer*>(&root);
+    const stormck_objectlist_params params{addressing_offsets, chunks_per_block, 0};
+    int rc;
+    if (!device) {
+        rc = stormck_lookup_host(store, &layout, r, root_type, &params, keys, stride, offsets, lens, len, n, flags, results,
+                                 nullptr, nullptr, &report, host_threads);
+    } else {
+        struct Workspace {
+            void* p = nullptr;
+            uint64_t bytes;
+            Workspace(uint64_t n_keys, uint32_t C) : bytes(stormck_lookup_workspace_bytes(n_keys, C)) {
+                detail::check(stormck_device_alloc(bytes, &p));
+            }
+            ~Workspace() { (void)stormck_device_free(p); }
+            Workspace(const Workspace&) = delete;
+            Workspace& operator=(const Workspace&) = delete;
+        } ws(n, chunks_per_block);
+        rc = stormck_lookup_device(store, &layout, r, root_type, &params, keys, stride, offsets, lens, len, n, flags,
+                                   results, nullptr, nullptr, ws.p, ws.bytes, &report, stream);
+    }
+    if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) throw DeviceError(rc);
+    return LookupResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
+}
+
 // ---- block layouts -------------------------------------------------------------
 
 // pointer.Block (blocks/pointer/block.go:10-13); PointersPerBlock = 1200 (params.go:6),

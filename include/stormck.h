@@ -655,6 +655,104 @@ int stormck_trace_host(const void* store, const stormck_scrub_layout* layout, co
                        uint32_t flags, stormck_trace_result* results, uint64_t* leaf_checksums,
                        stormck_trace_report* report, uint32_t host_threads);
 
+/* ---- lookup: keystore.GetObjectID for many keys at once ---------------------------
+ * keystore.GetObjectID (keystore/keystore.go:18-45) hashes the key to a tag, runs
+ * TraceTagForReading down to the objectlist leaf and probes that leaf by open addressing
+ * (findChunkPointerForKey and verifyKeyInChunks, keystore.go:112-133,178-208), returning
+ * ObjectLinks[index]. This is the three stages for n keys in one call: the key tags
+ * (stormck_key_tags_device's launch), the trace above over those tags with objectlist leaves
+ * of layout->objectlist_len bytes, and one probe per key.
+ *
+ * The leaf is objectlist.Block with C = chunks_per_block (blocks/objectlist/block.go:29-40):
+ * Blob at 0, KeyTagReminders at 32C, ObjectLinks at 40C, ChunkPointers at 48C,
+ * NextChunkPointers at 50C, ChunkPointerStates at 52C, NUsedChunks at 53C, FreeChunkIndex at
+ * 53C+2; (53C + 4 + 7) & ~7 bytes, which layout->objectlist_len must equal.
+ *
+ * The probe, storm's literally: seed = reminder % C; for i = 0..C-1, index = (seed +
+ * addressing_offsets[i]) % C and probes = i + 1. A Defined slot (state 1) matches when
+ * KeyTagReminders[index] == reminder and the chunk chain at ChunkPointers[index] spells the
+ * key: FOUND, object_id = ObjectLinks[index]. An Invalid slot (2) is remembered (the first
+ * one). A Free slot (0) ends the probe: ABSENT, index = the remembered Invalid slot or else
+ * this one, the slot findChunkPointerForKey hands EnsureObjectID. Any other state byte is
+ * skipped. All C slots seen: ABSENT, index = STORMCK_LOOKUP_NO_SLOT, probes = C.
+ * The chain: NextChunkPointers[chunk] > C marks the last chunk, which holds that value - C
+ * bytes, and the key matches iff exactly that many key bytes remain and are equal; otherwise
+ * 32 bytes are compared and the walk moves to the next chunk.
+ * The probe never reads outside the leaf and every loop is bounded (C slots; per item 8 chunks
+ * of 32 key bytes and the one that ends the chain). Where storm would index or slice out of
+ * range (a chunk index >= C, a remaining length above 32, a chunk that is not the last when
+ * fewer than 32 key bytes remain) the item does not match, the probe goes on and the key
+ * counts in n_malformed.
+ *
+ * The final status of a key, in this order: STORMCK_LOOKUP_KEY when its length is outside
+ * 1..256 (it is hashed and traced like any other, so report.trace counts it, but it is never
+ * probed and every other field of its result is 0, index NO_SLOT; its length's bytes must
+ * still be readable); the trace's status when that is not FOUND; else the probe's FOUND or
+ * ABSENT. With STORMCK_TRACE_LEAVES_UNVERIFIED the leaf is probed without being hashed
+ * (storm's warm GetObjectID); the bounds above make that safe on any bytes.
+ *
+ * The library ships no addressing table: storm's is rand.New(rand.NewSource(0)).Perm(600)
+ * from Go's math/rand, and the caller passes it (the Go binding passes
+ * objectlist.AddressingOffsets). */
+#define STORMCK_HAS_LOOKUP 1
+#define STORMCK_LOOKUP_KEY 7            /* key length outside 1..256 (keystore.go:23-28) */
+#define STORMCK_LOOKUP_NO_SLOT UINT32_MAX
+typedef struct stormck_objectlist_params {
+    const uint16_t* addressing_offsets; /* HOST pointer, chunks_per_block entries, a permutation of 0..C-1:
+                                           objectlist.AddressingOffsets */
+    uint32_t chunks_per_block;          /* 600; 10 under -tags test; 1..4096 */
+    uint32_t reserved;
+} stormck_objectlist_params;
+typedef struct stormck_lookup_result {  /* 32 bytes */
+    uint64_t object_id;   /* FOUND: ObjectLinks[index]; otherwise 0 */
+    uint64_t address;     /* the trace's final address for this key */
+    uint64_t reminder;    /* the trace's reminder */
+    uint32_t index;       /* FOUND: the item; probed and ABSENT: the insert slot or NO_SLOT; not probed: NO_SLOT */
+    uint16_t probes;      /* slots examined; 0 when the leaf was not probed */
+    uint8_t status, reserved;  /* STORMCK_TRACE_* numbers, or STORMCK_LOOKUP_KEY */
+} stormck_lookup_result;
+typedef struct stormck_lookup_report {
+    stormck_trace_report trace;  /* of the trace the call ran, unchanged */
+    uint64_t n_status[8];        /* keys per final status */
+    uint64_t n_probed, probes;   /* keys whose leaf was probed; sum of their probes */
+    uint64_t n_malformed;        /* keys that met at least one malformed chain */
+    uint64_t first_bad;          /* smallest key index ending MISMATCH, RANGE, TYPE, DEPTH or KEY; n if none */
+} stormck_lookup_report;
+
+/* Bytes of device workspace a lookup of n_keys needs: stormck_trace_workspace_bytes(n_keys)
+ * + 40 * ((n_keys + 7) & ~7) (the tags and the trace results, used when the caller passes
+ * none) + ((2 * chunks_per_block + 7) & ~7) (the table) + 256 (the counters). Host logic. */
+uint64_t stormck_lookup_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block);
+/* Look the n keys up in the key tree at `root` of the device-resident image d_store. Key i is
+ * addressed exactly as in stormck_key_tags_device: d_keys + (d_offsets ? d_offsets[i] :
+ * i * stride), (d_lens ? d_lens[i] : len) bytes, any alignment. d_results gets one result per
+ * key, in the keys' order; d_trace_results and d_tags (both optional, n entries) get the
+ * trace's results and the tags. Steps on `stream`: the key-tag launch, the trace's engine,
+ * k_lookup_probe with one lane per key, one pinned read-back. Synchronous, like the trace;
+ * n == 0 is a no-op with a zero report. flags: STORMCK_TRACE_LEAVES_UNVERIFIED.
+ * Returns STORMCK_EMISMATCH when first_bad < n, with that key's text in stormck_last_error():
+ * the trace's words for a trace status; for KEY storm's own, "key cannot be empty" or "maximum
+ * key component length exceeded, maximum: 256, actual: N". STORMCK_EINVAL, before any work,
+ * for every argument error of stormck_trace_device, a uniform len outside 1..256 with d_lens
+ * null (and n > 0), layout->objectlist_len != (53C + 4 + 7) & ~7, C outside 1..4096, a null table, a
+ * table that is not a permutation of 0..C-1, a workspace that is too small, misaligned
+ * pointers (8 bytes; d_lens 4). */
+int stormck_lookup_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                          uint8_t root_type, const stormck_objectlist_params* params, const void* d_keys,
+                          uint64_t stride, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t len, uint64_t n,
+                          uint32_t flags, stormck_lookup_result* d_results, stormck_trace_result* d_trace_results,
+                          uint64_t* d_tags, void* d_workspace, uint64_t workspace_bytes, stormck_lookup_report* report,
+                          void* stream);
+/* The same lookup over an image in host memory with host pointers throughout: stormck_xxh64,
+ * the trace's host leg and the same probe function on host_threads library pool threads
+ * (0 = the pool). Same rules, results, report and return codes; needs no device and no
+ * workspace, and is not routed. */
+int stormck_lookup_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                        uint8_t root_type, const stormck_objectlist_params* params, const void* keys, uint64_t stride,
+                        const uint64_t* offsets, const uint32_t* lens, uint32_t len, uint64_t n, uint32_t flags,
+                        stormck_lookup_result* results, stormck_trace_result* trace_results, uint64_t* tags,
+                        stormck_lookup_report* report, uint32_t host_threads);
+
 /* ---- synthetic data (benchmarks / tests) -----------------------------------
  * Word w of block i = splitmix64(seed ^ (((first + i) << 20) + w)), w < stride/8,
  * little-endian. stride % 16 == 0, d_dst 16-byte aligned. */

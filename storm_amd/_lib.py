@@ -104,6 +104,26 @@ class TraceReportStruct(ctypes.Structure):
                 ("first_bad", c_uint64), ("levels", c_uint32), ("reserved", c_uint32)]
 
 
+class ObjectListParamsStruct(ctypes.Structure):
+    """stormck_objectlist_params: objectlist.AddressingOffsets (a host pointer) and ChunksPerBlock."""
+
+    _fields_ = [("addressing_offsets", c_void_p), ("chunks_per_block", c_uint32), ("reserved", c_uint32)]
+
+
+class LookupResultStruct(ctypes.Structure):
+    """stormck_lookup_result: one key's object ID and where its lookup ended (32 bytes)."""
+
+    _fields_ = [("object_id", c_uint64), ("address", c_uint64), ("reminder", c_uint64), ("index", c_uint32),
+                ("probes", ctypes.c_uint16), ("status", c_uint8), ("reserved", c_uint8)]
+
+
+class LookupReportStruct(ctypes.Structure):
+    """stormck_lookup_report."""
+
+    _fields_ = [("trace", TraceReportStruct), ("n_status", c_uint64 * 8), ("n_probed", c_uint64), ("probes", c_uint64),
+                ("n_malformed", c_uint64), ("first_bad", c_uint64)]
+
+
 # name -> (restype, argtypes); mirrors include/stormck.h one to one.
 SIGNATURES = {
     "stormck_abi_version": (c_int, []),
@@ -192,6 +212,15 @@ SIGNATURES = {
     "stormck_trace_host": (
         c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_uint32, c_uint32, c_void_p,
                 c_uint64, c_uint32, c_void_p, c_void_p, POINTER(TraceReportStruct), c_uint32]),
+    "stormck_lookup_workspace_bytes": (c_uint64, [c_uint64, c_uint32]),
+    "stormck_lookup_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, POINTER(ObjectListParamsStruct),
+                c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p,
+                c_void_p, c_uint64, POINTER(LookupReportStruct), c_void_p]),
+    "stormck_lookup_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, POINTER(ObjectListParamsStruct),
+                c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p,
+                POINTER(LookupReportStruct), c_uint32]),
     "stormck_fill_synthetic_device": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p]),
 }
 

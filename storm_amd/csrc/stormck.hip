@@ -34,6 +34,7 @@
 #include "commit_plan.h"
 #include "dispatch.h"
 #include "kernels.h"
+#include "objlist_probe.h"
 #include "route_plan.h"
 #include "xxh64_host.h"
 
@@ -2996,5 +2997,38 @@ int stormck_debug_partial_quad_selftest(void) {
     return STORMCK_OK;
 }
 #endif
+
+}  // extern "C" (the lookup below calls stormck_key_tags_device and the trace's engine)
+
+namespace {
+
+#include "lookup.h"
+
+}  // namespace
+
+extern "C" {
+
+uint64_t stormck_lookup_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block) {
+    return lookup_workspace_bytes(n_keys, chunks_per_block);
+}
+
+int stormck_lookup_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                          uint8_t root_type, const stormck_objectlist_params* params, const void* d_keys,
+                          uint64_t stride, const uint64_t* d_offsets, const uint32_t* d_lens, uint32_t len, uint64_t n,
+                          uint32_t flags, stormck_lookup_result* d_results, stormck_trace_result* d_trace_results,
+                          uint64_t* d_tags, void* d_workspace, uint64_t workspace_bytes, stormck_lookup_report* report,
+                          void* stream) {
+    return lookup_device(d_store, layout, root, root_type, params, d_keys, stride, d_offsets, d_lens, len, n, flags,
+                         d_results, d_trace_results, d_tags, d_workspace, workspace_bytes, report, stream);
+}
+
+int stormck_lookup_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                        uint8_t root_type, const stormck_objectlist_params* params, const void* keys, uint64_t stride,
+                        const uint64_t* offsets, const uint32_t* lens, uint32_t len, uint64_t n, uint32_t flags,
+                        stormck_lookup_result* results, stormck_trace_result* trace_results, uint64_t* tags,
+                        stormck_lookup_report* report, uint32_t host_threads) {
+    return lookup_host(store, layout, root, root_type, params, keys, stride, offsets, lens, len, n, flags, results,
+                       trace_results, tags, report, host_threads);
+}
 
 }  // extern "C"
