@@ -2,6 +2,9 @@
 // (tests/test_lookup_sanitize.py): the malformed-chain and the probe-order cases on leaves, keys
 // and tables that each live in a heap allocation of exactly their size, so that a read past
 // any of them is a report. A plain C++17 program: no HIP, no library.
+// With a file name as its argument it also runs that corpus of recorded probes (the random
+// leaves of tests/lookup_util.py leaf_fuzz_case, answered by the Python probe; `corpus` below
+// has the format) and prints "ok" and the number of records.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -155,9 +158,58 @@ void probe_order(uint32_t C, const uint16_t* A) {
     }
 }
 
+// The corpus file tests/test_lookup_sanitize.py writes: records one after another with no
+// padding, every number little-endian. A record is a 32-byte head
+//   u32 C | u32 key_len | u64 reminder | u64 object_id | u32 index | u16 probes | u8 found | u8 malformed
+// (the last five: what the Python probe of tests/lookup_util.py answers), then the table (C
+// u16), the leaf (objlist_leaf_len(C) bytes) and the key (key_len bytes).
+struct CorpusHead {
+    uint32_t C, key_len;
+    uint64_t reminder, object_id;
+    uint32_t index;
+    uint16_t probes;
+    uint8_t found, malformed;
+};
+static_assert(sizeof(CorpusHead) == 32, "the head of a corpus record is 32 bytes");
+
+// Every record through both forms of the probe, its table, leaf and key each in a heap
+// allocation of exactly its size. Returns the number of records, -1 for a file that is not a corpus.
+long corpus(const char* path) {
+    std::FILE* f = std::fopen(path, "rb");
+    if (!f) return -1;
+    long n = 0;
+    CorpusHead h;
+    size_t got;
+    while ((got = std::fread(&h, 1, sizeof h, f)) == sizeof h) {
+        if (h.C == 0 || h.C > stormck::kObjlistMaxChunks || h.key_len == 0 || h.key_len > stormck::kObjlistMaxKey) break;
+        const size_t leaf_len = stormck::objlist_leaf_len(h.C);
+        std::unique_ptr<uint16_t[]> A(new uint16_t[h.C]);
+        std::unique_ptr<uint8_t[]> leaf(new uint8_t[leaf_len]);
+        std::unique_ptr<uint8_t[]> key(new uint8_t[h.key_len]);
+        if (std::fread(A.get(), 2, h.C, f) != h.C || std::fread(leaf.get(), 1, leaf_len, f) != leaf_len ||
+            std::fread(key.get(), 1, h.key_len, f) != h.key_len)
+            break;
+        const ProbeOut want{h.object_id, h.index, h.probes, h.found, h.malformed};
+        const ProbeOut plain = stormck::objlist_probe<false>(leaf.get(), h.C, A.get(), key.get(), h.key_len, h.reminder);
+        const ProbeOut batched = stormck::objlist_probe<true>(leaf.get(), h.C, A.get(), key.get(), h.key_len, h.reminder);
+        if (std::memcmp(&plain, &want, sizeof want) != 0 || std::memcmp(&batched, &want, sizeof want) != 0) {
+            std::printf("record %ld: want id %llu index %u probes %u found %u malformed %u; plain %llu %u %u %u %u; batched %llu %u %u %u %u\n",
+                        n, static_cast<unsigned long long>(want.object_id), want.index, want.probes, want.found,
+                        want.malformed, static_cast<unsigned long long>(plain.object_id), plain.index, plain.probes,
+                        plain.found, plain.malformed, static_cast<unsigned long long>(batched.object_id), batched.index,
+                        batched.probes, batched.found, batched.malformed);
+            ++failures;
+        }
+        ++n;
+    }
+    const bool whole = got == 0 && std::feof(f);  // the file ends where a record ends
+    std::fclose(f);
+    return whole ? n : -1;
+}
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
     for (uint32_t C : {1u, 2u, 10u, 600u, 4096u}) {
         // a permutation in an allocation of exactly C entries: i -> (7 i + 3) mod C, rotated for C = 1, 2
         std::unique_ptr<uint16_t[]> A(new uint16_t[C]);
@@ -165,7 +217,15 @@ int main() {
         probe_order(C, A.get());
         if (C >= 10) malformed_chains(C, A.get());
     }
+    long records = 0;
+    if (argc > 1 && (records = corpus(argv[1])) < 0) {
+        std::printf("%s is not a corpus of whole records\n", argv[1]);
+        return 1;
+    }
     if (failures) return 1;
-    std::printf("ok\n");
+    if (argc > 1)
+        std::printf("ok %ld\n", records);
+    else
+        std::printf("ok\n");
     return 0;
 }

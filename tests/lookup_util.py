@@ -9,7 +9,10 @@
 * ``KeyTree``: keys placed into the leaves of a tree by their tag digits (no split: a leaf that
   would overflow raises), laid out with scrub_util.Builder;
 * ``table``: addressing tables, seeded numpy permutations;
-* the designed cases both test files run (``CASES``), built once per process.
+* the designed cases both test files run (``CASES``), built once per process;
+* the fuzz of tests/test_lookup_fuzz.py and tests/test_lookup_fuzz_gpu.py: ``damaged_tree_case``
+  (the stored tree under scrub_util.random_damage) and ``leaf_fuzz_case`` (leaves whose fields
+  are edited at random), whose keys tests/test_lookup_sanitize.py also writes out as a corpus.
 """
 from __future__ import annotations
 
@@ -320,12 +323,17 @@ def host_trace_message(case: Case):
     return rep.message
 
 
+def reference_of(case: Case):
+    """The case's reference (results, report, message), once per case and process."""
+    if not hasattr(case, "_reference"):
+        case._reference = case.tree.reference(case.keys, case.verify_leaves)
+    return case._reference
+
+
 def check_against_reference(case: Case, records, report):
     """records and report (of either leg) against the pure-Python reference, then the case's
     own facts."""
-    if not hasattr(case, "_reference"):  # once per case and process
-        case._reference = case.tree.reference(case.keys, case.verify_leaves)
-    want, want_rep, message = case._reference
+    want, want_rep, message = reference_of(case)
     assert as_tuples(records) == want
     assert report.as_dict() == want_rep
     n = len(case.keys)
@@ -727,6 +735,143 @@ def production() -> Case:
         assert sum(leaf.next_pointer(c) == 632 for leaf in kt.leaves.values() for c in range(600)) == 40
         assert rep["trace"]["blocks_hashed"] == (1, 20) and max(r[4] for r in res) >= 20
     return Case(tree, stored + absent, check, mode="flat")
+
+
+# ---- fuzz (tests/test_lookup_fuzz.py, tests/test_lookup_fuzz_gpu.py) -------------------------------
+
+DAMAGED_TREE_SEEDS = 30
+DAMAGED_TREE_EDITS = (1, 3, 10)
+FUZZ_STREAM = 200  # second word of the rngs' seeds: apart from the scrub's (0..4) and the trace's fuzz
+
+
+@functools.lru_cache(maxsize=None)
+def _stored_index():
+    t = _stored_tree()
+    return su.reference_scrub(t.img, t.lay, t.root, t.root_type, OBJECTLIST, 0)[2]
+
+
+def assert_inside(tree: Tree, keys):
+    """trace_util.assert_inside for the keys' tags in a key tree, on the host before any upload;
+    a probe of any block below n_blocks, leaf or not, stays inside that block."""
+    as_traced = tu.Tree(tree.img, tree.lay, tree.root, tree.root_type, OBJECTLIST)
+    tu.assert_inside(as_traced, as_traced.reference([o.xxh64(k) for k in keys])[0])
+    assert ks.leaf_len(tree.C) <= tree.lay.block_size
+
+
+@functools.lru_cache(maxsize=None)
+def _damaged_tree(seed):
+    """(Tree, keys, mode): the stored tree of 120 keys under su.random_damage, resealed; its keys
+    shuffled among 20 absent ones and, in odd seeds, one key of length 0 or 257."""
+    _, stored = _stored()
+    t, index = _stored_tree(), _stored_index()
+    rng = np.random.default_rng([seed, FUZZ_STREAM])
+    img = t.img.copy()
+    keep_bad = su.random_damage(img, t.lay, index, rng, DAMAGED_TREE_EDITS[seed % 3], whole_store=False)
+    cs = su.reseal(img, t.lay, index, keep_bad)
+    tree = Tree(su.frozen(img), t.lay, (cs, t.root[1]), t.root_type, t.C, t.A, t.address_of)
+    keys = stored + _absent_keys(rng, 20)
+    keys = [keys[int(i)] for i in rng.permutation(len(keys))]
+    if seed % 2:
+        bad = rng.integers(0, 256, 257 * int(rng.integers(2)), dtype=np.uint8).tobytes()
+        keys.insert(int(rng.integers(len(keys) + 1)), bad)
+    assert_inside(tree, keys)
+    return tree, keys, "rows+lens" if seed % 2 else "flat"
+
+
+@functools.lru_cache(maxsize=None)
+def damaged_tree_case(seed, verify_leaves=True) -> Case:
+    """Lookup on a damaged key tree. Unverified, a re-typed or re-addressed entry hands the probe
+    a block that is no objectlist leaf, and a flipped leaf is probed as it is."""
+    tree, keys, mode = _damaged_tree(seed)
+    return Case(tree, keys, None, mode=mode, verify_leaves=verify_leaves)
+
+
+LEAF_FUZZ = ((10, range(60)), (40, range(60)), (600, range(4)))  # (C, seeds)
+LEAF_FUZZ_LENGTHS = (1, 7, 8, 9, 31, 32, 33, 40, 63, 64, 65, 96, 255, 256)  # both sides of 8 and 32: the compare runs in 8-byte words
+LEAF_FUZZ_EDITS = ("state", "reminder", "chunk pointer", "next pointer", "chunk bytes", "defined", "no free slot")
+_LEAF_FUZZ_LAYOUTS = {10: TEST_LAYOUT, 40: C40_LAYOUT, 600: PRODUCTION_LAYOUT}
+
+
+def _edit_leaf(leaf: Leaf, rng, pool, reminders):
+    """One random field edit of LEAF_FUZZ_EDITS."""
+    C = leaf.C
+    pick = lambda values: values[int(rng.integers(len(values)))]  # noqa: E731
+    below_C = lambda: int(rng.integers(C))  # noqa: E731
+    what = pick(LEAF_FUZZ_EDITS)
+    if what == "state":
+        leaf.state(below_C(), pick((0, 1, 1, 2, 3, 255)))
+    elif what == "reminder":
+        leaf.reminder(below_C(), pick(reminders))
+    elif what == "chunk pointer":
+        leaf.chunk_pointer(below_C(), pick((below_C(), C, C + 1, 65535)))
+    elif what == "next pointer":
+        chunk = below_C()
+        leaf.next_pointer(chunk, pick((below_C(), chunk, C, C + int(rng.integers(1, 33)), C + 32, C + 33, 65535)))
+    elif what == "chunk bytes":
+        key, chunk = pick(pool), below_C()
+        piece = key[32 * int(rng.integers((len(key) + 31) // 32)):][:32]
+        leaf.b[32 * chunk:32 * chunk + 32] = piece.ljust(32, b"\0")
+    elif what == "defined":
+        index = below_C()
+        leaf.state(index, DEFINED)
+        leaf.reminder(index, pick(reminders))
+        leaf.chunk_pointer(index, below_C())
+    else:  # every Free state byte becomes another: a probe that finds no match sees all C slots
+        for index in range(C):
+            if leaf.state(index) == FREE:
+                leaf.state(index, pick((DEFINED, INVALID, 3, 255)))
+
+
+def _leaf_pool(kt: KeyTree, slot, rng):
+    """Five different keys of LEAF_FUZZ_LENGTHS that locate in the leaf at (slot,)."""
+    pool = []
+    while len(pool) < 5:
+        n = int(LEAF_FUZZ_LENGTHS[rng.integers(len(LEAF_FUZZ_LENGTHS))])
+        if n == 1:  # 256 keys in all: one of those that locate here, if any is left (else another length)
+            here = [bytes([b]) for b in range(256) if kt.locate(bytes([b]))[0] == (slot,) and bytes([b]) not in pool]
+            pool += [here[int(rng.integers(len(here)))]] if here else []
+        else:
+            pool.append(key_in(kt, (slot,), rng, n))
+    return pool
+
+
+@functools.lru_cache(maxsize=None)
+def _leaf_fuzz(C, seed):
+    """(Tree, keys, mode): one pointer block over ten leaves (three at C = 600), each with a pool
+    of five keys that locate there, about two thirds of them inserted properly while chunks
+    last, then 0..8 random field edits. KeyTree.build hashes the leaves after the edits, so the
+    leaves verify and every key is probed."""
+    kt = KeyTree(_LEAF_FUZZ_LAYOUTS[C], table(C, seed), depth=1)
+    rng = np.random.default_rng([seed, FUZZ_STREAM + C])
+    keys = []
+    for slot in range(3 if C == 600 else 10):
+        leaf = kt.leaf((slot,))
+        pool = _leaf_pool(kt, slot, rng)
+        for j, k in enumerate(pool):
+            if rng.random() < 2 / 3:
+                try:
+                    kt.add(k, 1000 * slot + j + 1)
+                except OverflowError:  # the chunks (or the slots) have run out
+                    pass
+        reminders = [kt.locate(k)[1] for k in pool]
+        for _ in range(int(rng.integers(9))):
+            _edit_leaf(leaf, rng, pool, reminders)
+        keys += pool
+    keys = [keys[int(i)] for i in rng.permutation(len(keys))]
+    tree = kt.build()
+    assert_inside(tree, keys)
+    return tree, keys, "rows+lens" if seed % 2 else "flat"
+
+
+@functools.lru_cache(maxsize=None)
+def leaf_fuzz_case(C, seed, verify_leaves=True) -> Case:
+    """Lookup in leaves whose every field may be arbitrary: all pool keys, shuffled."""
+    tree, keys, mode = _leaf_fuzz(C, seed)
+    return Case(tree, keys, None, mode=mode, verify_leaves=verify_leaves)
+
+
+def leaf_fuzz_ids():
+    return [(C, seed) for C, seeds in LEAF_FUZZ for seed in seeds]
 
 
 CASES = {"edge lengths": edge_lengths, "decoys": decoys, "probe order": probe_order,

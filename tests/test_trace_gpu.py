@@ -33,13 +33,14 @@ def device_tags(tags):
     return torch.from_numpy(tu.tags_u64(tags).view(np.int64)).cuda()
 
 
-def same_everywhere(tree, tags, image, verify_leaves=True, stream=0):
-    """Device == host leg == reference: results, report, leaf checksums, code and message."""
+def same_everywhere(tree, tags, image, verify_leaves=True, stream=0, workspace=None):
+    """Device == host leg == reference: results, report, leaf checksums, code and message.
+    `workspace`: a device tensor the device call uses as it is (tests/test_trace_fuzz_gpu.py)."""
     want, want_rep, refs, want_cs = tree.reference(tags, verify_leaves)
     hres, hrep = trace.trace_host(tree.img, *tree.args(), tu.tags_u64(tags), tree.leaf_len, verify_leaves,
                                   leaf_checksums=True)
     dres, drep = trace.trace_device(image, *tree.args(), device_tags(tags), tree.leaf_len, verify_leaves, stream,
-                                    leaf_checksums=True)
+                                    workspace, leaf_checksums=True)
     res = trace.results_numpy(dres)
     assert res.tobytes() == hres.tobytes()
     assert tu.as_tuples(res) == want

@@ -3,7 +3,8 @@
 ``reference_trace`` is a pure-Python walk of one tag at a time with the C oracle's XXH64: the
 rules of include/stormck.h "trace", literally and in their order. It is the reference for
 every result field, every report field and the set of distinct references. The images come
-from tests/scrub_util.py.
+from tests/scrub_util.py. ``fuzz_case`` is the seeded damage fuzz of tests/test_trace_fuzz.py and
+tests/test_trace_fuzz_gpu.py.
 """
 from __future__ import annotations
 
@@ -96,9 +97,16 @@ class Tree:
     def args(self):
         return self.lay, self.root[:2] + (2,), self.root_type, self.leaf_kind
 
+    memo = None  # a dict: the references of this tree are kept, per tag list (by identity) and verify_leaves
+
     def reference(self, tags, verify_leaves=True):
-        return reference_trace(self.img, self.lay, self.root, self.root_type, self.leaf_kind, tags, self.leaf_len,
-                               verify_leaves)
+        if self.memo is not None and (id(tags), verify_leaves) in self.memo:
+            return self.memo[id(tags), verify_leaves][1]
+        ref = reference_trace(self.img, self.lay, self.root, self.root_type, self.leaf_kind, tags, self.leaf_len,
+                              verify_leaves)
+        if self.memo is not None:
+            self.memo[id(tags), verify_leaves] = (tags, ref)  # holds the list: its id stays its own
+        return ref
 
 
 @functools.lru_cache(maxsize=None)
@@ -206,6 +214,74 @@ def entry_type_3(img, lay, index):
     parent, slot, off, toff = su.pointer_entry(img, lay, index, level=3)
     img[toff] = 3
     return dict(parent=parent, slot=slot, old=su._u64(img, off + 8))
+
+
+# ---- seeded damage fuzz (tests/test_trace_fuzz.py, tests/test_trace_fuzz_gpu.py) -----------------
+
+FUZZ_IMAGES = ("f10", "f64", "f65")
+FUZZ_SEEDS = 40
+FUZZ_TAG_COUNTS = (65, 257, 1500, 4099)  # a wave and a bit, a workgroup and a bit, several workgroups
+FUZZ_STREAM = 100                        # second word of the rng's seed from here on: the scrub's fuzz uses 0..4
+fuzz_statuses = {}  # (image, seed) -> the reference's n_status (leaves verified), for the conditions
+
+
+def fuzz_tags(name, seed, rng):
+    """About 60 % present tags drawn with repetition, 20 % random odd 64-bit values and 20 %
+    present + k * F**j (j in 1..5, k in 0..2): walks that share the upper path with a present
+    tag and part from it deeper, to end ABSENT at a free entry or FOUND with a non-zero reminder."""
+    F, present = su.TREE_SHAPES[name][0], np.array(list(su.TREE_SHAPES[name][1]), dtype=np.uint64)
+    n = FUZZ_TAG_COUNTS[seed % len(FUZZ_TAG_COUNTS)]
+    tags = [int(t) for t in present[rng.integers(0, len(present), n)]]
+    what = rng.random(n)
+    for i in range(n):
+        if what[i] < 0.2:
+            tags[i] = (int(rng.integers(0, 2 ** 63, dtype=np.uint64)) * 2 + 1) & U64
+        elif what[i] < 0.4:
+            tags[i] = (tags[i] + int(rng.integers(3)) * F ** int(rng.integers(1, 6))) & U64
+    return tags
+
+
+def assert_inside(tree, results):
+    """What the device cases rely on, asserted on the host before any upload, from the reference's
+    `results` (leaves verified) for the tags to be traced: the image has exactly n_blocks + SLACK
+    blocks, and every reference a walk ends at names a block of it; a block that is hashed lies
+    below n_blocks. (The references a walk passes through are below n_blocks by the RANGE rule. A
+    bit flip can leave a larger address in a pointer block; that block then mismatches and no
+    walk reads its entries.)"""
+    lay = tree.lay
+    assert tree.img.dtype == np.uint8 and tree.img.size == (lay.n_blocks + su.SLACK) * lay.block_size
+    assert 0 < tree.root[1] < lay.n_blocks
+    for address, _, _, _, _, status in results:
+        assert address < lay.n_blocks + su.SLACK
+        assert 0 < address < lay.n_blocks or status not in (FOUND, MISMATCH)
+
+
+@functools.lru_cache(maxsize=2)  # the two verify_leaves settings of one case follow one another
+def fuzz_case(name, seed):
+    """(Tree, tags): tree `name` after su.random_damage with the scrub's edit counts, resealed
+    so that only the deliberate damage is wrong, and the tags of fuzz_tags."""
+    t, index = shape(name), su.intact_index(name)
+    rng = np.random.default_rng([seed, FUZZ_STREAM + FUZZ_IMAGES.index(name)])
+    n_edits = su.FUZZ_EDITS[seed % len(su.FUZZ_EDITS)]
+    if t.lay.n_blocks < 1000:  # small images: at most an edit per four blocks
+        n_edits = max(1, min(n_edits, t.lay.n_blocks // 4))
+    img = t.img.copy()
+    keep_bad = su.random_damage(img, t.lay, index, rng, n_edits, whole_store=False)
+    cs = su.reseal(img, t.lay, index, keep_bad, lens=su.kind_lens(t.lay, BLOB, t.leaf_len))
+    tree = Tree(su.frozen(img), t.lay, (cs, t.root[1]), t.root_type, BLOB, t.leaf_len)
+    tree.memo = {}
+    tags = fuzz_tags(name, seed, rng)
+    results, report, _, _ = tree.reference(tags)
+    assert_inside(tree, results)
+    fuzz_statuses[name, seed] = report["n_status"]
+    return tree, tags
+
+
+def fuzz_n_status(name, seed):
+    """The reference's n_status of a fuzz case with the leaves verified, once per process."""
+    if (name, seed) not in fuzz_statuses:
+        fuzz_case(name, seed)
+    return fuzz_statuses[name, seed]
 
 
 def tags_under(index, address):
