@@ -180,6 +180,24 @@ def test_binding_on_gpu_matches_storm_commit_loop(arena):
     assert a["data"] == b["data"]
 
 
+@pytest.mark.gpu
+def test_binding_on_gpu_small_geometry_seeds():
+    """Storm-made forests at the small geometry (1 KiB slots, fan-out 10, trees nested under
+    leaves: several heights of a few hundred blocks), seeds 1-6, arena in HBM."""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    dev = torch.device("cuda", 0)
+    for seed in range(1, 7):
+        a = _storm(_workload(seed=seed, **SMALL))
+        c = _workload(seed=seed, **SMALL)
+        b = _binding(c, _device_run(c, dev))
+        assert a["dirty"] == b["dirty"] == 0, seed
+        assert a["sing"] == b["sing"], seed
+        assert a["store"] == b["store"], seed
+        assert a["metas"] == b["metas"], seed
+        assert a["data"] == b["data"], seed
+
+
 def _routed_run(c, legs):
     """blocks.CommitBatch as the Go binding calls it: stormck_commit on the registered
     cache.data, which picks the leg (recorded in `legs`)."""

@@ -14,6 +14,7 @@ import pytest
 
 from oracle import oracle as o
 from storm_amd import commit as sc
+from tests.commit_util import _fast_random_bytes, arrange, assert_inside  # noqa: F401
 from tests.conftest import hx, load_golden
 
 
@@ -198,25 +199,6 @@ def test_device_commit_matches_fixture(dev):
     assert singularity_step(out, g["revision"], last2) == hx(g["singularity_checksum"])
 
 
-def arrange(b: np.ndarray, how: str, rng) -> np.ndarray:
-    """Permute the dirty list and remap parent indices. "shuffled": parents may precede
-    children; "upper_shuffled": level 0 (the leaves) stays a prefix in index order, the
-    pointer blocks after it are shuffled; "children_first": as built."""
-    n_leaves = int((b["type"] == sc.LEAF).sum())
-    if how == "children_first":
-        return b.copy()
-    if how == "shuffled":
-        perm = rng.permutation(len(b))
-    else:
-        perm = np.concatenate([np.arange(n_leaves), n_leaves + rng.permutation(len(b) - n_leaves)])
-    inv = np.empty_like(perm)
-    inv[perm] = np.arange(len(b))
-    bp = b[perm].copy()
-    has = bp["parent"] >= 0
-    bp["parent"][has] = inv[bp["parent"][has]]
-    return bp
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("how", ["shuffled", "upper_shuffled", "children_first"])
 @pytest.mark.parametrize("n,fanout,slot", [(1, 10, 1024), (10, 10, 1024), (11, 10, 1024), (999, 10, 1024),
@@ -276,19 +258,6 @@ def test_device_commit_streaming_level_mixed_lengths(dev, n):
     assert np.array_equal(cs, want_cs)
     assert np.array_equal(bp["address"], ref_b["address"]) and last2 == want_last
     assert np.array_equal(out, ref_arena)
-
-
-def assert_inside(b, nbytes, shift=0):
-    """Every byte range the commit reads or writes lies inside an arena of nbytes: blocks,
-    24-byte origin Pointers and origin type bytes (`shift`: bytes before the arena)."""
-    assert int((b["data_offset"] + b["length"]).max()) + shift <= nbytes
-    has = b["origin_pointer"] != np.uint64(sc.NO_ORIGIN)
-    assert int(b["origin_pointer"][has].max()) + 24 + shift <= nbytes
-    assert int(b["origin_type"][has].max()) + 1 + shift <= nbytes
-
-
-def _fast_random_bytes(rng, nbytes):
-    return rng.integers(0, 1 << 63, size=(nbytes + 7) // 8, dtype=np.int64).view(np.uint8)[:nbytes]
 
 
 @pytest.mark.gpu
