@@ -147,6 +147,26 @@ def build_order_pass(force: bool = False) -> str:
     return ORDER_PASS
 
 
+# tests/test_stream_kernels_gpu.py (not product): the persistent streaming kernels launched directly
+STREAM_KERNELS = os.path.join(ROOT, "tests", "hip", "libstreamkernels.so")
+STREAM_KERNELS_DEBUG = os.path.join(ROOT, "tests", "hip", "libstreamkernels_debug.so")
+
+
+def build_stream_kernels(force: bool = False) -> str:
+    """tests/hip/libstreamkernels.so: k_xxh64_glds_skew and k_xxh64_glds_var on the caller's
+    buffers and grid (test only), and libstreamkernels_debug.so, the same file with
+    -DSTORMCK_DEBUG_QUAD (every quad merge checked for a partially active quad)."""
+    srcs = [os.path.join(ROOT, "tests", "hip", "stream_kernels.hip"), os.path.join(CSRC, "kernels.h"),
+            os.path.join(CSRC, "xxh64_dev.h"), os.path.join(ROOT, "include", "stormck.h")]
+    for out, extra in ((STREAM_KERNELS, []), (STREAM_KERNELS_DEBUG, ["-DSTORMCK_DEBUG_QUAD"])):
+        if force or not _newer(out, srcs):
+            tmp = out + ".tmp"
+            subprocess.run([hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-shared", *extra,
+                            "-o", tmp, srcs[0]], check=True)
+            os.replace(tmp, out)
+    return STREAM_KERNELS
+
+
 def build_probe(force: bool = False) -> str:
     """Build the design probes (tools/probe*.hip) next to their sources."""
     built = []

@@ -5,9 +5,12 @@ DPP (kernels.h quad_bcast: update_dpp, bound_ctrl = false, old = 0). A source la
 is not in exec then reads as 0: the checksum is silently wrong. A round-3 variant hit
 exactly this (DESIGN_LOG.md §4, "Quad merges"). The debug build (tools/libstormck_debug.so,
 -DSTORMCK_DEBUG_QUAD) counts every merge made with a partially active quad. This test
-runs every kernel family of the shipped dispatch through that build in a child process,
-checks each result against the oracle, and requires the count to be zero. Its self-test
-kernel merges with 3 lanes of every quad off, so the counter is seen to work."""
+runs the kernel families the shipped dispatch takes up to 60,000 blocks through that build in
+a child process, checks each result against the oracle, and requires the count to be zero.
+The persistent kernels (k_xxh64_glds_skew, the persistent k_xxh64_glds_var), which the
+dispatch takes only from tens of GB, go through the same check by direct launch in
+tests/test_stream_kernels_gpu.py. Its self-test kernel merges with 3 lanes of every quad
+off, so the counter is seen to work."""
 import json
 import os
 import subprocess
@@ -56,8 +59,9 @@ res["selftest"] = count()
 rng = np.random.default_rng(5)
 bad = []
 # every batch class of launch_checksum (plan_checksum, storm_amd/csrc/dispatch.h): wide, wide-multi (5 / 8 per CU), quad spread,
-# quad, LDS-DMA 1/3/8 waves and the persistent skewed form; uniform, per-block lengths,
-# gathered offsets, unaligned rows; checksum and verify
+# quad, LDS-DMA 1/3/8 waves; uniform, per-block lengths, gathered offsets, unaligned rows;
+# checksum and verify. (No batch here is large enough for the two persistent kernels: they run
+# through the same check by direct launch, tests/test_stream_kernels_gpu.py.)
 for n, slot in [(1, 4096), (100, 4096), (1200, 32768), (2000, 32768), (3000, 8192), (8000, 4096), (9300, 32768),
                 (12000, 4096), (30000, 1024), (60000, 2048)]:
     host = o.fill_synthetic(n, slot, 0)
