@@ -416,6 +416,152 @@ inline LookupResult GetObjectIDs(const void* store, const stormck_scrub_layout& 
     return LookupResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
 }
 
+// Objects (stormck_objects_device / stormck_objects_host): objectstore.GetObject for n object
+// IDs at once in the object tree at `root`: the trace above with blob leaves, the open-addressing
+// probe of each ID's leaf (findObject) and the move of the found objects into rows. ID i is the
+// u64 at ids + i * id_stride (32: the object_id fields of a stormck_lookup_result array, in
+// place); results gets one stormck_object_result per ID; the first object_size bytes of row i,
+// objects + i * out_stride, get the object when it is FOUND and zeros otherwise (objects may be
+// null). object_size is unsafe.Sizeof(T) of the Go type stored, sizeof(T) here for a T laid out as
+// Go lays it out. `device` = true: store, ids, results and objects are device memory and the call
+// is queued on `stream`; false: host memory on host_threads pool threads. A damaged tree is not an
+// exception: the statuses and the report say what is wrong, and ObjectsResult::message is the
+// text of the first bad ID's error.
+struct ObjectsResult {
+    stormck_objects_report report;
+    std::string message;  // "" when no ID ended MISMATCH, RANGE, TYPE or DEPTH
+    bool ok(uint64_t n) const { return report.first_bad >= n; }
+};
+inline ObjectsResult GetObjects(const void* store, const stormck_scrub_layout& layout, const Pointer& root,
+                                BlockType root_type, uint32_t objects_per_block, uint32_t object_size, const void* ids,
+                                uint64_t id_stride, uint64_t n, stormck_object_result* results, void* objects,
+                                uint64_t out_stride, bool device, uint32_t flags = 0, void* stream = nullptr,
+                                uint32_t host_threads = 0) {
+    stormck_objects_report report{};
+    const stormck_pointer* r = reinterpret_cast<const stormck_pointer*>(&root);
+    const stormck_blob_params params{objects_per_block, object_size};
+    int rc;
+    if (!device) {
+        rc = stormck_objects_host(store, &layout, r, root_type, &params, ids, id_stride, n, flags, results, objects,
+                                  out_stride, &report, host_threads);
+    } else {
+        struct Workspace {
+            void* p = nullptr;
+            uint64_t bytes;
+            explicit Workspace(uint64_t n_ids) : bytes(stormck_objects_workspace_bytes(n_ids)) {
+                detail::check(stormck_device_alloc(bytes, &p));
+            }
+            ~Workspace() { (void)stormck_device_free(p); }
+            Workspace(const Workspace&) = delete;
+            Workspace& operator=(const Workspace&) = delete;
+        } ws(n);
+        rc = stormck_objects_device(store, &layout, r, root_type, &params, ids, id_stride, n, flags, results, objects,
+                                    out_stride, ws.p, ws.bytes, &report, stream);
+    }
+    if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) throw DeviceError(rc);
+    return ObjectsResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
+}
+// The typed form: objects[i] is the T of ids[i], T{} where there is none (Go's zero T).
+template <class T>
+inline ObjectsResult GetObjects(const void* store, const stormck_scrub_layout& layout, const Pointer& root,
+                                BlockType root_type, uint32_t objects_per_block, const ObjectID* ids, uint64_t n,
+                                stormck_object_result* results, T* objects, bool device, uint32_t flags = 0,
+                                void* stream = nullptr, uint32_t host_threads = 0) {
+    static_assert(std::is_trivially_copyable_v<T> && alignof(T) <= 8, "a Go value type of alignment at most 8");
+    return GetObjects(store, layout, root, root_type, objects_per_block, static_cast<uint32_t>(sizeof(T)), ids, 8, n, results,
+                      objects, sizeof(T), device, flags, stream, host_threads);
+}
+
+// Spaces (stormck_spaces_device / stormck_spaces_host): spacestore.GetSpace for n space IDs at
+// once in the space tree at `root`: the trace above with spacelist leaves and findSpace's probe
+// of each ID's leaf. results gets one stormck_space_result per ID: for a FOUND (Defined) space
+// the roots and block types of its key tree and object tree, which GetObjectIDs and GetObjects
+// take as they are. addressing_offsets is spacelist.AddressingOffsets (always a host array,
+// layout.spaces_per_block entries). `device` = true: store, ids and results are device memory.
+struct SpacesResult {
+    stormck_spaces_report report;
+    std::string message;  // "" when no ID ended MISMATCH, RANGE, TYPE or DEPTH
+    bool ok(uint64_t n) const { return report.first_bad >= n; }
+};
+inline SpacesResult GetSpaces(const void* store, const stormck_scrub_layout& layout, const Pointer& root,
+                              BlockType root_type, const uint16_t* addressing_offsets, const uint64_t* ids, uint64_t n,
+                              stormck_space_result* results, bool device, uint32_t flags = 0, void* stream = nullptr,
+                              uint32_t host_threads = 0) {
+    stormck_spaces_report report{};
+    const stormck_pointer* r = reinterpret_cast<const stormck_pointer*>(&root);
+    int rc;
+    if (!device) {
+        rc = stormck_spaces_host(store, &layout, r, root_type, addressing_offsets, ids, n, flags, results, &report,
+                                 host_threads);
+    } else {
+        struct Workspace {
+            void* p = nullptr;
+            uint64_t bytes;
+            Workspace(uint64_t n_ids, uint32_t S) : bytes(stormck_spaces_workspace_bytes(n_ids, S)) {
+                detail::check(stormck_device_alloc(bytes, &p));
+            }
+            ~Workspace() { (void)stormck_device_free(p); }
+            Workspace(const Workspace&) = delete;
+            Workspace& operator=(const Workspace&) = delete;
+        } ws(n, layout.spaces_per_block);
+        rc = stormck_spaces_device(store, &layout, r, root_type, addressing_offsets, ids, n, flags, results, ws.p, ws.bytes,
+                                   &report, stream);
+    }
+    if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) throw DeviceError(rc);
+    return SpacesResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
+}
+
+// Get (stormck_get_device / stormck_get_host): storm.Get for n keys of space `space_id` in one
+// call, from the store's singularity: the space, the lookup over the keys, the objects of the
+// keys that were found. Keys are addressed as in GetObjectIDs; results gets one stormck_get_result
+// per key (stage: 0 space, 1 key, 2 object, where the walk ended) and row i of objects the
+// object, or object_size zero bytes. space_offsets and key_offsets are spacelist's and
+// objectlist's AddressingOffsets (host arrays). `device` = true: store, keys, offsets, lens,
+// results and objects are device memory.
+struct GetResult {
+    stormck_get_report report;
+    std::string message;  // "" when no key ended MISMATCH, RANGE, TYPE, DEPTH or KEY
+    bool ok(uint64_t n) const { return report.first_bad >= n; }
+};
+inline GetResult Get(const void* store, const stormck_scrub_layout& layout, uint64_t space_id,
+                     const uint16_t* space_offsets, const uint16_t* key_offsets, uint32_t chunks_per_block,
+                     uint32_t objects_per_block, uint32_t object_size, const void* keys, uint64_t stride,
+                     const uint64_t* offsets, const uint32_t* lens, uint32_t len, uint64_t n, stormck_get_result* results,
+                     void* objects, uint64_t out_stride, bool device, uint32_t flags = 0, void* stream = nullptr,
+                     uint32_t host_threads = 0) {
+    stormck_get_report report{};
+    const stormck_get_params params{space_offsets, {key_offsets, chunks_per_block, 0}, {objects_per_block, object_size}};
+    int rc;
+    if (!device) {
+        rc = stormck_get_host(store, &layout, space_id, &params, keys, stride, offsets, lens, len, n, flags, results, objects,
+                              out_stride, &report, host_threads);
+    } else {
+        struct Workspace {
+            void* p = nullptr;
+            uint64_t bytes;
+            Workspace(uint64_t n_keys, uint32_t C) : bytes(stormck_get_workspace_bytes(n_keys, C)) {
+                detail::check(stormck_device_alloc(bytes, &p));
+            }
+            ~Workspace() { (void)stormck_device_free(p); }
+            Workspace(const Workspace&) = delete;
+            Workspace& operator=(const Workspace&) = delete;
+        } ws(n, chunks_per_block);
+        rc = stormck_get_device(store, &layout, space_id, &params, keys, stride, offsets, lens, len, n, flags, results,
+                                objects, out_stride, ws.p, ws.bytes, &report, stream);
+    }
+    if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) throw DeviceError(rc);
+    return GetResult{report, rc == STORMCK_EMISMATCH ? stormck_last_error() : ""};
+}
+
+// blob.Object[T] (blocks/blob/block.go:18-22) as Go lays it out for a T of alignment at most 8:
+// what objectstore's findObject views a blob leaf's Data as.
+template <class T>
+struct alignas(8) BlobObject {
+    uint64_t ObjectIDTagReminder;
+    T Object;
+    uint8_t State;  // 0 Free, 1 Defined, 2 Invalid
+};
+
 // ---- block layouts -------------------------------------------------------------
 
 // pointer.Block (blocks/pointer/block.go:10-13); PointersPerBlock = 1200 (params.go:6),

@@ -753,6 +753,235 @@ int stormck_lookup_host(const void* store, const stormck_scrub_layout* layout, c
                         stormck_lookup_result* results, stormck_trace_result* trace_results, uint64_t* tags,
                         stormck_lookup_report* report, uint32_t host_threads);
 
+/* ---- objects: objectstore.GetObject for many object IDs at once --------------------
+ * objectstore.GetObject (objectstore/objectstore.go:15-38) runs TraceTagForReading with the
+ * object ID as the tag down to a blob leaf and probes that leaf by open addressing (findObject,
+ * objectstore.go:92-123), returning the slot's Object when the slot is Defined. This is the two
+ * stages, and the copy of the objects into dense rows, for n object IDs in one call: the trace
+ * above over the IDs with blob leaves of layout->blob_len bytes, one probe per ID, one row per
+ * ID.
+ *
+ * The leaf is blob.Block (blocks/blob/block.go:25-29): Data[blob_len - 8], then NUsedSlots as
+ * u64. findObject views Data as N = objects_per_block values of Go's blob.Object[T]. With
+ * S = object_size = unsafe.Sizeof(T), slot k lies at Data + k * stride:
+ *   ObjectIDTagReminder u64 at 0, Object at 8 (S bytes), State byte at 8 + S,
+ *   stride = (8 + S + 1 + 7) & ~7.
+ * Go places each field at the next multiple of its alignment and rounds the struct's size up to
+ * its largest alignment: the u64 makes that 8, T at 8 is aligned for every alignment up to 8,
+ * S is a multiple of T's alignment so the State byte follows T directly, and 8 + S + 1 rounds
+ * up to 8. This holds for every T of alignment at most 8.
+ *
+ * The probe, storm's literally: start = reminder % N; for j = 0..N-1, k = (start + j) % N and
+ * probes = j + 1. A Defined slot (state 1) with ObjectIDTagReminder == reminder: FOUND,
+ * index = k. An Invalid slot (2) is remembered (the first one). A Free slot (0) ends the probe:
+ * ABSENT, index = the remembered Invalid slot or else this one, the slot findObject hands
+ * SetObject. Any other state byte is skipped. All N slots seen: ABSENT, index =
+ * STORMCK_LOOKUP_NO_SLOT, probes = N. Every index is below N and N * stride <= blob_len - 8 is
+ * checked first, so the probe never leaves the leaf and its loop is bounded.
+ *
+ * The final status of an ID: the trace's status when that is not FOUND (index NO_SLOT, probes
+ * 0); else the probe's FOUND or ABSENT. With STORMCK_TRACE_LEAVES_UNVERIFIED the leaf is
+ * probed and read without being hashed (storm's warm GetObject); the bounds above make that
+ * safe on any bytes.
+ *
+ * Row i of the objects array is at objects + i * out_stride. Its first S bytes are the object
+ * when ID i is FOUND and zeros otherwise (Go returns the zero T); bytes S..out_stride of a row
+ * are never written. objects may be NULL: only the results are written. */
+#define STORMCK_HAS_OBJECTS 1
+typedef struct stormck_blob_params {
+    uint32_t objects_per_block;  /* N, 1..4095 */
+    uint32_t object_size;        /* S = unsafe.Sizeof(T), at least 1; N * stride <= layout->blob_len - 8 */
+} stormck_blob_params;
+typedef struct stormck_object_result {  /* 32 bytes */
+    uint64_t object_id;   /* the ID as read */
+    uint64_t address;     /* the trace's final address for this ID */
+    uint64_t reminder;    /* the trace's reminder */
+    uint32_t index;       /* FOUND: the slot; probed and ABSENT: the insert slot or NO_SLOT; not probed: NO_SLOT */
+    uint16_t probes;      /* slots examined; 0 when the leaf was not probed */
+    uint8_t status, reserved;  /* STORMCK_TRACE_* numbers */
+} stormck_object_result;
+typedef struct stormck_objects_report {
+    stormck_trace_report trace;  /* of the trace the call ran, unchanged */
+    uint64_t n_status[8];        /* IDs per final status */
+    uint64_t n_probed, probes;   /* IDs whose leaf was probed; sum of their probes */
+    uint64_t first_bad;          /* smallest index ending MISMATCH, RANGE, TYPE or DEPTH; n if none */
+} stormck_objects_report;
+
+/* Bytes of device workspace a call with n_ids needs: stormck_trace_workspace_bytes(n_ids)
+ * + 32 * ((n_ids + 7) & ~7) (the trace results) + 256 (the counters). Host logic. */
+uint64_t stormck_objects_workspace_bytes(uint64_t n_ids);
+/* Get the objects of n IDs from the object tree at `root` of the device-resident image d_store.
+ * ID i is the u64 at d_ids + i * id_stride (id_stride a multiple of 8, at least 8: 32 reads the
+ * object_id field of a stormck_lookup_result array in place). d_results gets one result per ID,
+ * in the IDs' order, and must not overlap d_ids: with id_stride above 8 its first 8 n bytes hold
+ * the gathered IDs while the trace runs (the trace reads dense tags, the workspace formula
+ * below has no 8 n bytes that are free during the trace, and a trace that ends every tag at its
+ * root writes trace result t as it reads tag t, so the trace-results region cannot lend them);
+ * after a call that fails with another code than STORMCK_EMISMATCH d_results is unspecified; d_objects (optional) gets the rows, n * out_stride bytes at any
+ * alignment. Steps on `stream`: the trace's engine, k_object_fetch with one lane per ID (the
+ * probe, the counters, then the move of the objects: each lane its own, or the
+ * whole wave one row at a time, by the object's size: DESIGN.md "Objects"), one pinned
+ * read-back. Synchronous, like the trace; n == 0 is a no-op with a zero report. flags:
+ * STORMCK_TRACE_LEAVES_UNVERIFIED.
+ * Returns STORMCK_EMISMATCH when first_bad < n, with the trace's text for that ID in
+ * stormck_last_error(); ABSENT is not an error. STORMCK_EINVAL, before any work, for every
+ * argument error of stormck_trace_device, N outside 1..4095, S == 0, N * stride >
+ * layout->blob_len - 8, out_stride < S (when d_objects is given), id_stride below 8 or not a
+ * multiple of 8, a workspace that is too small, misaligned pointers (d_store, d_ids, d_results,
+ * d_workspace: 8 bytes). */
+int stormck_objects_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                           uint8_t root_type, const stormck_blob_params* params, const void* d_ids, uint64_t id_stride,
+                           uint64_t n, uint32_t flags, stormck_object_result* d_results, void* d_objects,
+                           uint64_t out_stride, void* d_workspace, uint64_t workspace_bytes,
+                           stormck_objects_report* report, void* stream);
+/* The same over an image in host memory with host pointers throughout: the trace's host leg and
+ * the same probe function on host_threads library pool threads (0 = the pool). Same rules,
+ * results, rows, report and return codes; needs no device and no workspace, and is not routed. */
+int stormck_objects_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                         uint8_t root_type, const stormck_blob_params* params, const void* ids, uint64_t id_stride,
+                         uint64_t n, uint32_t flags, stormck_object_result* results, void* objects, uint64_t out_stride,
+                         stormck_objects_report* report, uint32_t host_threads);
+
+/* ---- spaces: spacestore.GetSpace for space IDs --------------------------------------
+ * spacestore.GetSpace (spacestore/spacestore.go:14-42) runs TraceTagForReading with the space ID
+ * as the tag down to a spacelist leaf and probes that leaf by open addressing (findSpace,
+ * spacestore.go:92-121); a Defined space holds the two tree roots of the space. This is both
+ * stages for n space IDs in one call: the trace above over the IDs (n dense u64) with spacelist
+ * leaves of (72 * spaces_per_block + 2 + 7) & ~7 bytes, and one probe per ID.
+ *
+ * A space is 72 bytes (blocks/spacelist/block.go:21-31): SpaceIDTagReminder at 0, NextObjectID
+ * at 8, KeyStorePointer at 16, ObjectStorePointer at 40, KeyStoreBlockType at 64,
+ * ObjectStoreBlockType at 65, State at 66.
+ *
+ * The probe, storm's literally, with S = layout->spaces_per_block: seed = reminder % S; for
+ * i = 0..S-1, index = (seed + addressing_offsets[i]) % S and probes = i + 1. A Defined space
+ * (state 1) with SpaceIDTagReminder == reminder: FOUND. An Invalid space (2) is remembered (the
+ * first one). A Free space (0) ends the probe: ABSENT, index = the remembered Invalid slot or
+ * else this one, the slot findSpace hands EnsureSpace. Any other state byte is skipped. All S
+ * slots seen: ABSENT, index = STORMCK_LOOKUP_NO_SLOT, probes = S. Every index is below S, so the
+ * probe never leaves the leaf and its loop is bounded: STORMCK_TRACE_LEAVES_UNVERIFIED is safe
+ * on any bytes. ABSENT is storm's "space does not exist".
+ *
+ * addressing_offsets is the caller's spacelist.AddressingOffsets: a HOST pointer to
+ * spaces_per_block entries, checked to be a permutation of 0..S-1. The library ships no table,
+ * for the reason the lookup gives. S is at most 32768 here (storm computes the index in uint16). */
+#define STORMCK_HAS_SPACES 1
+typedef struct stormck_space_result {  /* 88 bytes */
+    stormck_pointer key_root;     /* FOUND: KeyStorePointer; otherwise zeros */
+    stormck_pointer object_root;  /* FOUND: ObjectStorePointer; otherwise zeros */
+    uint64_t next_object_id;      /* FOUND: NextObjectID; otherwise 0 */
+    uint64_t address;             /* the trace's final address for this ID */
+    uint64_t reminder;            /* the trace's reminder */
+    uint32_t index;               /* FOUND: the slot; probed and ABSENT: the insert slot or NO_SLOT; not probed: NO_SLOT */
+    uint16_t probes;              /* slots examined; 0 when the leaf was not probed */
+    uint8_t key_type, object_type;  /* FOUND: the two block types; otherwise 0 */
+    uint8_t status;               /* STORMCK_TRACE_* numbers */
+    uint8_t reserved[7];
+} stormck_space_result;
+typedef struct stormck_spaces_report {
+    stormck_trace_report trace;  /* of the trace the call ran, unchanged */
+    uint64_t n_status[8];        /* IDs per final status */
+    uint64_t n_probed, probes;   /* IDs whose leaf was probed; sum of their probes */
+    uint64_t first_bad;          /* smallest index ending MISMATCH, RANGE, TYPE or DEPTH; n if none */
+} stormck_spaces_report;
+
+/* Bytes of device workspace a call with n_ids needs: stormck_trace_workspace_bytes(n_ids)
+ * + 32 * ((n_ids + 7) & ~7) (the trace results) + ((2 * spaces_per_block + 7) & ~7) (the
+ * table) + 256 (the counters). Host logic. */
+uint64_t stormck_spaces_workspace_bytes(uint64_t n_ids, uint32_t spaces_per_block);
+/* Get the spaces of the n IDs at d_ids from the space tree at `root` of the device-resident
+ * image d_store. Steps on `stream`: the table's upload, the trace's engine, k_space_probe with
+ * one lane per ID, one pinned read-back. Synchronous, like the trace; n == 0 is a no-op with a
+ * zero report. flags: STORMCK_TRACE_LEAVES_UNVERIFIED. Returns STORMCK_EMISMATCH when
+ * first_bad < n, with the trace's text for that ID in stormck_last_error(). STORMCK_EINVAL,
+ * before any work, for every argument error of stormck_trace_device, spaces_per_block above
+ * 32768, a null table, a table that is not a permutation, a workspace that is too small,
+ * misaligned pointers (8 bytes). */
+int stormck_spaces_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                          uint8_t root_type, const uint16_t* addressing_offsets, const uint64_t* d_ids, uint64_t n,
+                          uint32_t flags, stormck_space_result* d_results, void* d_workspace, uint64_t workspace_bytes,
+                          stormck_spaces_report* report, void* stream);
+/* The same over an image in host memory with host pointers throughout. Same rules, results,
+ * report and return codes; needs no device and no workspace, and is not routed. */
+int stormck_spaces_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                        uint8_t root_type, const uint16_t* addressing_offsets, const uint64_t* ids, uint64_t n,
+                        uint32_t flags, stormck_space_result* results, stormck_spaces_report* report,
+                        uint32_t host_threads);
+
+/* ---- get: storm.Get for many keys of one space ---------------------------------------
+ * storm.Get (storm.go:32-58) is spacestore.GetSpace, keystore.GetObjectID and
+ * objectstore.GetObject, one after the other. This is the three stages for n keys of one space
+ * in one call, from the store's singularity block:
+ *   1. the singularity (block 0, 72 bytes) is read and verified on the host as the scrub
+ *      verifies it; a failure is MISMATCH at stage 0 for every key;
+ *   2. "spaces" above with n = 1: space_id from the singularity's space origin;
+ *   3. "lookup" above over the keys from the space's key root;
+ *   4. the keys whose lookup ended FOUND are compacted, in their order, into a dense ID array;
+ *   5. "objects" above over those IDs from the space's object root;
+ *   6. results and object rows go back to key order; rows of keys without an object are zeros
+ *      over object_size bytes, bytes past object_size of a row are never written, d_objects may
+ *      be NULL.
+ * The status of a key, with the stage where its walk ended: the space's status when that is not
+ * FOUND (stage 0; all keys share it; ABSENT there is storm's "space does not exist"); else the
+ * lookup's status when that is not FOUND (stage 1); else the object stage's status (stage 2: a
+ * key that is present whose object slot is not Defined ends ABSENT there).
+ * first_bad is the smallest key index ending MISMATCH, RANGE, TYPE, DEPTH or KEY; the call then
+ * returns STORMCK_EMISMATCH with that key's text in stormck_last_error(): the scrub's words for
+ * the singularity, the spaces call's, the lookup's, or the object trace's (the compaction keeps
+ * the keys' order, so the object trace's own first bad ID is that key).
+ * STORMCK_TRACE_LEAVES_UNVERIFIED applies to objectlist and blob leaves alike (storm's warm Get);
+ * the spacelist leaf is always verified. */
+#define STORMCK_HAS_GET 1
+typedef struct stormck_get_params {
+    const uint16_t* space_offsets;   /* HOST pointer: spacelist.AddressingOffsets, layout->spaces_per_block entries */
+    stormck_objectlist_params keys;  /* the lookup's */
+    stormck_blob_params objects;     /* the objects call's */
+} stormck_get_params;
+typedef struct stormck_get_result {  /* 32 bytes */
+    uint64_t object_id;       /* the lookup's object ID; 0 when the key has none */
+    uint64_t key_address;     /* stage 1 and 2: the lookup's final address for the key; stage 0: 0 */
+    uint64_t object_address;  /* stage 2: the object trace's final address; otherwise 0 */
+    uint32_t index;           /* stage 2: the object stage's index; stage 1: the lookup's; stage 0: NO_SLOT */
+    uint8_t stage;            /* 0 space, 1 key, 2 object: where the walk ended */
+    uint8_t status;           /* STORMCK_TRACE_* numbers, or STORMCK_LOOKUP_KEY */
+    uint16_t reserved;
+} stormck_get_result;
+typedef struct stormck_get_report {
+    stormck_space_result space;    /* the one space's result (zeros when the singularity failed) */
+    stormck_lookup_report lookup;  /* of the lookup the call ran, unchanged (zeros, first_bad n, when it did not run) */
+    uint64_t n_selected;           /* keys whose lookup ended FOUND: the object stage's IDs */
+    uint64_t n_status[8];          /* the object stage: IDs per status */
+    uint64_t blocks_hashed[2];     /* the object stage's trace: pointer blocks, leaves */
+    uint64_t bytes_hashed;         /* ... its bytes */
+    uint64_t probes;               /* ... sum of its probes */
+    uint32_t levels, reserved;     /* ... its tree levels */
+    uint64_t n_found;              /* keys that ended FOUND at stage 2 */
+    uint64_t first_bad;            /* in key indices; n if none */
+} stormck_get_report;
+
+/* Bytes of device workspace a call with n_keys needs: stormck_lookup_workspace_bytes(n_keys,
+ * chunks_per_block) (the lookup's, which the spaces and the objects stage reuse)
+ * + stormck_spaces_workspace_bytes(1, 32768) when that is larger + 80 * ((n_keys + 7) & ~7) (the
+ * lookup's results, the dense IDs, the object stage's results, each key's place among them and
+ * each ID's key) + 8 * (n_keys / 256 + 2) (the compaction's counts) + 128 (the space). Host logic. */
+uint64_t stormck_get_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block);
+/* Get the objects of n keys (addressed as in stormck_lookup_device) of space space_id in the
+ * device-resident store d_store. d_results gets one result per key, d_objects (optional) one row
+ * per key, out_stride apart. Synchronous; n == 0 is a no-op with a zero report. STORMCK_EINVAL,
+ * before any work, for every argument error of the three calls it contains, a workspace that is
+ * too small, misaligned pointers. */
+int stormck_get_device(const void* d_store, const stormck_scrub_layout* layout, uint64_t space_id,
+                       const stormck_get_params* params, const void* d_keys, uint64_t stride, const uint64_t* d_offsets,
+                       const uint32_t* d_lens, uint32_t len, uint64_t n, uint32_t flags, stormck_get_result* d_results,
+                       void* d_objects, uint64_t out_stride, void* d_workspace, uint64_t workspace_bytes,
+                       stormck_get_report* report, void* stream);
+/* The same over a store in host memory with host pointers throughout, through the three host
+ * legs. Same rules, results, rows, report and return codes; needs no device and no workspace. */
+int stormck_get_host(const void* store, const stormck_scrub_layout* layout, uint64_t space_id,
+                     const stormck_get_params* params, const void* keys, uint64_t stride, const uint64_t* offsets,
+                     const uint32_t* lens, uint32_t len, uint64_t n, uint32_t flags, stormck_get_result* results,
+                     void* objects, uint64_t out_stride, stormck_get_report* report, uint32_t host_threads);
+
 /* ---- synthetic data (benchmarks / tests) -----------------------------------
  * Word w of block i = splitmix64(seed ^ (((first + i) << 20) + w)), w < stride/8,
  * little-endian. stride % 16 == 0, d_dst 16-byte aligned. */

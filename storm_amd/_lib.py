@@ -124,6 +124,63 @@ class LookupReportStruct(ctypes.Structure):
                 ("n_malformed", c_uint64), ("first_bad", c_uint64)]
 
 
+class BlobParamsStruct(ctypes.Structure):
+    """stormck_blob_params: objectsPerBlock and unsafe.Sizeof(T) of the blob leaves."""
+
+    _fields_ = [("objects_per_block", c_uint32), ("object_size", c_uint32)]
+
+
+class ObjectResultStruct(ctypes.Structure):
+    """stormck_object_result: where one object ID's GetObject ended (32 bytes)."""
+
+    _fields_ = [("object_id", c_uint64), ("address", c_uint64), ("reminder", c_uint64), ("index", c_uint32),
+                ("probes", ctypes.c_uint16), ("status", c_uint8), ("reserved", c_uint8)]
+
+
+class ObjectsReportStruct(ctypes.Structure):
+    """stormck_objects_report."""
+
+    _fields_ = [("trace", TraceReportStruct), ("n_status", c_uint64 * 8), ("n_probed", c_uint64), ("probes", c_uint64),
+                ("first_bad", c_uint64)]
+
+
+class SpaceResultStruct(ctypes.Structure):
+    """stormck_space_result: one space ID's two tree roots and where its GetSpace ended (88 bytes)."""
+
+    _fields_ = [("key_root", PointerStruct), ("object_root", PointerStruct), ("next_object_id", c_uint64),
+                ("address", c_uint64), ("reminder", c_uint64), ("index", c_uint32), ("probes", ctypes.c_uint16),
+                ("key_type", c_uint8), ("object_type", c_uint8), ("status", c_uint8), ("reserved", c_uint8 * 7)]
+
+
+class SpacesReportStruct(ctypes.Structure):
+    """stormck_spaces_report."""
+
+    _fields_ = [("trace", TraceReportStruct), ("n_status", c_uint64 * 8), ("n_probed", c_uint64), ("probes", c_uint64),
+                ("first_bad", c_uint64)]
+
+
+class GetParamsStruct(ctypes.Structure):
+    """stormck_get_params: the spaces' table (a host pointer), the lookup's params, the objects call's."""
+
+    _fields_ = [("space_offsets", c_void_p), ("keys", ObjectListParamsStruct), ("objects", BlobParamsStruct)]
+
+
+class GetResultStruct(ctypes.Structure):
+    """stormck_get_result: where one key's storm.Get ended (32 bytes)."""
+
+    _fields_ = [("object_id", c_uint64), ("key_address", c_uint64), ("object_address", c_uint64), ("index", c_uint32),
+                ("stage", c_uint8), ("status", c_uint8), ("reserved", ctypes.c_uint16)]
+
+
+class GetReportStruct(ctypes.Structure):
+    """stormck_get_report."""
+
+    _fields_ = [("space", SpaceResultStruct), ("lookup", LookupReportStruct), ("n_selected", c_uint64),
+                ("n_status", c_uint64 * 8), ("blocks_hashed", c_uint64 * 2), ("bytes_hashed", c_uint64),
+                ("probes", c_uint64), ("levels", c_uint32), ("reserved", c_uint32), ("n_found", c_uint64),
+                ("first_bad", c_uint64)]
+
+
 # name -> (restype, argtypes); mirrors include/stormck.h one to one.
 SIGNATURES = {
     "stormck_abi_version": (c_int, []),
@@ -221,6 +278,30 @@ SIGNATURES = {
         c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, POINTER(ObjectListParamsStruct),
                 c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_void_p,
                 POINTER(LookupReportStruct), c_uint32]),
+    "stormck_objects_workspace_bytes": (c_uint64, [c_uint64]),
+    "stormck_objects_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, POINTER(BlobParamsStruct),
+                c_void_p, c_uint64, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64,
+                POINTER(ObjectsReportStruct), c_void_p]),
+    "stormck_objects_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, POINTER(BlobParamsStruct),
+                c_void_p, c_uint64, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64, POINTER(ObjectsReportStruct),
+                c_uint32]),
+    "stormck_spaces_workspace_bytes": (c_uint64, [c_uint64, c_uint32]),
+    "stormck_spaces_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_void_p, c_void_p, c_uint64,
+                c_uint32, c_void_p, c_void_p, c_uint64, POINTER(SpacesReportStruct), c_void_p]),
+    "stormck_spaces_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), POINTER(PointerStruct), c_uint8, c_void_p, c_void_p, c_uint64,
+                c_uint32, c_void_p, POINTER(SpacesReportStruct), c_uint32]),
+    "stormck_get_workspace_bytes": (c_uint64, [c_uint64, c_uint32]),
+    "stormck_get_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
+                c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64, c_void_p, c_uint64,
+                POINTER(GetReportStruct), c_void_p]),
+    "stormck_get_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
+                c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64, POINTER(GetReportStruct), c_uint32]),
     "stormck_fill_synthetic_device": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p]),
 }
 

@@ -34,6 +34,8 @@
 #include "commit_plan.h"
 #include "dispatch.h"
 #include "kernels.h"
+#include "blob_probe.h"
+#include "space_probe.h"
 #include "objlist_probe.h"
 #include "route_plan.h"
 #include "xxh64_host.h"
@@ -3003,6 +3005,9 @@ int stormck_debug_partial_quad_selftest(void) {
 namespace {
 
 #include "lookup.h"
+#include "objects.h"
+#include "spaces.h"
+#include "get.h"
 
 }  // namespace
 
@@ -3029,6 +3034,65 @@ int stormck_lookup_host(const void* store, const stormck_scrub_layout* layout, c
                         stormck_lookup_report* report, uint32_t host_threads) {
     return lookup_host(store, layout, root, root_type, params, keys, stride, offsets, lens, len, n, flags, results,
                        trace_results, tags, report, host_threads);
+}
+
+uint64_t stormck_objects_workspace_bytes(uint64_t n_ids) { return objects_workspace_bytes(n_ids); }
+
+int stormck_objects_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                           uint8_t root_type, const stormck_blob_params* params, const void* d_ids, uint64_t id_stride,
+                           uint64_t n, uint32_t flags, stormck_object_result* d_results, void* d_objects,
+                           uint64_t out_stride, void* d_workspace, uint64_t workspace_bytes,
+                           stormck_objects_report* report, void* stream) {
+    return objects_device(d_store, layout, root, root_type, params, d_ids, id_stride, n, flags, d_results, d_objects,
+                          out_stride, d_workspace, workspace_bytes, report, stream);
+}
+
+int stormck_objects_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                         uint8_t root_type, const stormck_blob_params* params, const void* ids, uint64_t id_stride,
+                         uint64_t n, uint32_t flags, stormck_object_result* results, void* objects, uint64_t out_stride,
+                         stormck_objects_report* report, uint32_t host_threads) {
+    return objects_host(store, layout, root, root_type, params, ids, id_stride, n, flags, results, objects, out_stride,
+                        report, host_threads);
+}
+
+uint64_t stormck_spaces_workspace_bytes(uint64_t n_ids, uint32_t spaces_per_block) {
+    return spaces_workspace_bytes(n_ids, spaces_per_block);
+}
+
+int stormck_spaces_device(const void* d_store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                          uint8_t root_type, const uint16_t* addressing_offsets, const uint64_t* d_ids, uint64_t n,
+                          uint32_t flags, stormck_space_result* d_results, void* d_workspace, uint64_t workspace_bytes,
+                          stormck_spaces_report* report, void* stream) {
+    return spaces_device(d_store, layout, root, root_type, addressing_offsets, d_ids, n, flags, d_results, d_workspace,
+                         workspace_bytes, report, stream);
+}
+
+int stormck_spaces_host(const void* store, const stormck_scrub_layout* layout, const stormck_pointer* root,
+                        uint8_t root_type, const uint16_t* addressing_offsets, const uint64_t* ids, uint64_t n,
+                        uint32_t flags, stormck_space_result* results, stormck_spaces_report* report,
+                        uint32_t host_threads) {
+    return spaces_host(store, layout, root, root_type, addressing_offsets, ids, n, flags, results, report, host_threads);
+}
+
+uint64_t stormck_get_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block) {
+    return get_workspace_bytes(n_keys, chunks_per_block);
+}
+
+int stormck_get_device(const void* d_store, const stormck_scrub_layout* layout, uint64_t space_id,
+                       const stormck_get_params* params, const void* d_keys, uint64_t stride, const uint64_t* d_offsets,
+                       const uint32_t* d_lens, uint32_t len, uint64_t n, uint32_t flags, stormck_get_result* d_results,
+                       void* d_objects, uint64_t out_stride, void* d_workspace, uint64_t workspace_bytes,
+                       stormck_get_report* report, void* stream) {
+    return get_device(d_store, layout, space_id, params, d_keys, stride, d_offsets, d_lens, len, n, flags, d_results,
+                      d_objects, out_stride, d_workspace, workspace_bytes, report, stream);
+}
+
+int stormck_get_host(const void* store, const stormck_scrub_layout* layout, uint64_t space_id,
+                     const stormck_get_params* params, const void* keys, uint64_t stride, const uint64_t* offsets,
+                     const uint32_t* lens, uint32_t len, uint64_t n, uint32_t flags, stormck_get_result* results,
+                     void* objects, uint64_t out_stride, stormck_get_report* report, uint32_t host_threads) {
+    return get_host(store, layout, space_id, params, keys, stride, offsets, lens, len, n, flags, results, objects,
+                    out_stride, report, host_threads);
 }
 
 }  // extern "C"
