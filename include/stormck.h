@@ -982,6 +982,118 @@ int stormck_get_host(const void* store, const stormck_scrub_layout* layout, uint
                      const uint32_t* lens, uint32_t len, uint64_t n, uint32_t flags, stormck_get_result* results,
                      void* objects, uint64_t out_stride, stormck_get_report* report, uint32_t host_threads);
 
+/* ---- update: storm.Set for keys that already have an object, as a new revision ----------
+ * storm.Set (storm.go:61-79) is EnsureSpace, EnsureObjectID and SetObject, then Cache.Commit.
+ * On a key that already has an object, EnsureSpace and EnsureObjectID find what GetSpace and
+ * GetObjectID find, and SetObject (objectstore/objectstore.go:41-90) sees a Defined slot: it
+ * stores the object and commits the trace; NUsedSlots, the state byte and the reminder stay,
+ * and no block is allocated or split. Cache.Commit then rehashes the touched blob leaves, their
+ * ancestors in the object tree, the spacelist leaf that holds the space's ObjectStorePointer, its
+ * ancestors and the singularity, and moves each of them to a fresh address
+ * (cache/cache.go:113-118). This is that case for n keys of one space in one call, in place in
+ * the image; everything else of Set (inserts, slots that are not Defined, splits, EnsureSpace)
+ * stays storm's. Row i of the objects array is at + i * in_stride, at any alignment; its first
+ * S = params->objects.object_size bytes are the new object of key i. flags must be 0: every leaf
+ * is verified, because the call re-signs the leaves it writes and must not launder damage.
+ *
+ * A. Locate (nothing is written). The get above runs over the keys with no rows. results[i]
+ *    holds the get's values on the old store. If the get ends STORMCK_EMISMATCH the call
+ *    returns that code and text, every action is NONE and the store is byte for byte as it was.
+ * B. Select. A key is applicable when it ended FOUND at stage 2. Every other key (an absent
+ *    space, an absent key, a key whose object slot is not Defined: storm would insert there)
+ *    has action NONE; the caller sends those to storm's own Set. Among the applicable keys that
+ *    name one slot (object_address, index) the one with the largest i is WRITTEN, the others
+ *    are SUPERSEDED: storm's serial loop, where the last Set wins. With no WRITTEN key the call
+ *    returns STORMCK_OK with the store untouched, Revision and LastAllocatedBlock included.
+ *    Deviation: storm's Commit would still bump the revision; a batch that changes nothing
+ *    makes no revision here.
+ * C. Dirty forest. The dirty blocks are the distinct blob leaves of WRITTEN keys, every
+ *    pointer block on those object IDs' walks from the space's object root, the spacelist leaf
+ *    that holds the space's record, and every pointer block on the space ID's walk from the
+ *    singularity's space origin. The height of a dirty block is 0 without a dirty child, else 1
+ *    + the largest height among its dirty children (the spacelist leaf's dirty child is the
+ *    object tree's root block, which may itself be a leaf). Order: ascending height, within a
+ *    height ascending old address. With L = the singularity's LastAllocatedBlock and D dirty
+ *    blocks, the k-th block in that order (k from 0) moves to address L + 1 + k. Deviation:
+ *    every dirty block moves. storm moves a block only when BirthRevision <= Revision, which
+ *    holds for every block of a store that storm's commit wrote; the call does not look at the
+ *    field. If L + D >= layout->n_blocks (the image's capacity) or L >= layout->n_blocks the
+ *    call returns STORMCK_ENOSPC with the store untouched.
+ * D. Write. Steps 1 to 3 go only to addresses above L; the singularity is last.
+ *    1. Each dirty block's whole block_size bytes are copied from its old address to its new.
+ *    2. The S bytes of each WRITTEN key's row are stored at the object of slot `index` in the
+ *       new leaf. Nothing else of the slot changes, and NUsedSlots does not.
+ *    3. The commit above runs over the new copies, children first by height: each dirty block
+ *       is hashed at its new address over its kind's length, and Pointer{checksum, new address,
+ *       Revision + 1} and the block's unchanged type byte are stored into the origin in the
+ *       parent's new copy: entry `slot` of a pointer block; ObjectStorePointer @72k+40 and its
+ *       type @72k+65 of the space's record; SpacePointer @32 and its type @56 of the
+ *       singularity's host copy.
+ *    4. The singularity: Revision + 1, LastAllocatedBlock = L + D, Checksum over the 72 bytes
+ *       with the field zeroed, written as 72 bytes to block 0 as the call's last store. The rest
+ *       of block 0 is not touched.
+ * Three consequences. The old snapshot survives: every byte of blocks 1..L is unchanged, and
+ * putting the old 72 bytes back into block 0 gives back the old store. Failure is all or
+ * nothing: a HIP error before step 4 leaves the old revision valid. Writes stay in bounds: no
+ * byte at or beyond n_blocks * block_size is written, and none in blocks (L + D, n_blocks).
+ * Everything storm shares between revisions stays shared: the key tree, untouched object
+ * leaves, other spaces. The old blocks are not reclaimed. */
+#define STORMCK_HAS_UPDATE 1
+#define STORMCK_ENOSPC (-6)  /* update: the image has no room for the dirty blocks */
+enum { STORMCK_UPDATE_NONE = 0, STORMCK_UPDATE_WRITTEN = 1, STORMCK_UPDATE_SUPERSEDED = 2 };
+typedef struct stormck_update_result {  /* 32 bytes: stormck_get_result with its reserved field split */
+    uint64_t object_id;
+    uint64_t key_address;
+    uint64_t object_address;  /* on the old store */
+    uint32_t index;
+    uint8_t stage;
+    uint8_t status;
+    uint8_t action;           /* STORMCK_UPDATE_* */
+    uint8_t reserved;
+} stormck_update_result;
+typedef struct stormck_update_report {
+    stormck_get_report get;          /* of the get the call ran, unchanged */
+    uint64_t n_written, n_superseded;
+    uint64_t n_dirty[4];             /* dirty blocks per STORMCK_SCRUB_* kind (objectlist: always 0) */
+    uint64_t bytes_copied;           /* D * block_size */
+    uint64_t bytes_hashed;           /* of the dirty blocks at their kinds' lengths, and the singularity's 72 */
+    uint64_t revision;               /* the singularity's after the call, when the get returned STORMCK_OK; otherwise 0 */
+    uint64_t last_allocated;         /* likewise */
+    uint64_t first_new;              /* L + 1, or 0 when nothing moved */
+    uint32_t heights, reserved;      /* distinct heights of the dirty forest */
+} stormck_update_report;
+
+/* Bytes of device workspace a call with n_keys needs: stormck_get_workspace_bytes(n_keys,
+ * chunks_per_block) rounded up to 8 + 12 * T (the table of distinct slots and of distinct
+ * blocks, T = the smallest power of two that is at least 64 and at least 2 * n_keys) + 24 *
+ * (((n_keys + 7) & ~7) + 72) (the dirty blocks of one tree level, and the space's path) + 64
+ * (the counters): O(n_keys), whatever the image's size. Host logic. */
+uint64_t stormck_update_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block);
+/* Update the objects of n keys (addressed as in stormck_lookup_device) of space space_id in the
+ * device-resident store d_store, which is written in place. Steps on `stream`: the get; the
+ * winner of every slot (k_update_claim, k_update_actions); the dirty blocks, one tree level per
+ * launch (k_update_walk), read back as one small record per dirty block; the plan on the host;
+ * k_update_copy, k_object_store (each lane its own row, or the whole wave one row at a time, by
+ * the object's size as in "objects"); the device commit; the singularity's 72 bytes.
+ * Synchronous; n == 0 is a no-op with a zero report. A block deeper than 64 pointer blocks
+ * ends the get DEPTH, so the walks are bounded. STORMCK_EINVAL, before any work, for every
+ * argument error of the get, flags != 0, in_stride < S, a null d_objects with n > 0, a
+ * workspace that is too small, misaligned pointers (8 bytes: d_store, d_results, d_offsets,
+ * d_workspace; 4: d_lens), a stream that is being captured. */
+int stormck_update_device(void* d_store, const stormck_scrub_layout* layout, uint64_t space_id,
+                          const stormck_get_params* params, const void* d_keys, uint64_t stride, const uint64_t* d_offsets,
+                          const uint32_t* d_lens, uint32_t len, uint64_t n, const void* d_objects, uint64_t in_stride,
+                          uint32_t flags, stormck_update_result* d_results, void* d_workspace, uint64_t workspace_bytes,
+                          stormck_update_report* report, void* stream);
+/* The same over a store in host memory with host pointers throughout: the get's host leg, the
+ * same plan and the commit's host leg on host_threads library pool threads (0 = the pool). Same
+ * rules, results, image bytes, report and return codes; needs no device and no workspace. */
+int stormck_update_host(void* store, const stormck_scrub_layout* layout, uint64_t space_id,
+                        const stormck_get_params* params, const void* keys, uint64_t stride, const uint64_t* offsets,
+                        const uint32_t* lens, uint32_t len, uint64_t n, const void* objects, uint64_t in_stride,
+                        uint32_t flags, stormck_update_result* results, stormck_update_report* report,
+                        uint32_t host_threads);
+
 /* ---- synthetic data (benchmarks / tests) -----------------------------------
  * Word w of block i = splitmix64(seed ^ (((first + i) << 20) + w)), w < stride/8,
  * little-endian. stride % 16 == 0, d_dst 16-byte aligned. */

@@ -22,6 +22,7 @@ EHIP = -2
 ENODEV = -3
 ENOMEM = -4
 EMISMATCH = -5
+ENOSPC = -6
 
 # arena placement modes of stormck_device_alloc_placed: the probe build only (measured and
 # rejected in round 4; the product allocates with hipMalloc, stormck_device_alloc)
@@ -181,6 +182,21 @@ class GetReportStruct(ctypes.Structure):
                 ("first_bad", c_uint64)]
 
 
+class UpdateResultStruct(ctypes.Structure):
+    """stormck_update_result: stormck_get_result with its reserved field split (32 bytes)."""
+
+    _fields_ = [("object_id", c_uint64), ("key_address", c_uint64), ("object_address", c_uint64), ("index", c_uint32),
+                ("stage", c_uint8), ("status", c_uint8), ("action", c_uint8), ("reserved", c_uint8)]
+
+
+class UpdateReportStruct(ctypes.Structure):
+    """stormck_update_report."""
+
+    _fields_ = [("get", GetReportStruct), ("n_written", c_uint64), ("n_superseded", c_uint64), ("n_dirty", c_uint64 * 4),
+                ("bytes_copied", c_uint64), ("bytes_hashed", c_uint64), ("revision", c_uint64),
+                ("last_allocated", c_uint64), ("first_new", c_uint64), ("heights", c_uint32), ("reserved", c_uint32)]
+
+
 # name -> (restype, argtypes); mirrors include/stormck.h one to one.
 SIGNATURES = {
     "stormck_abi_version": (c_int, []),
@@ -302,6 +318,15 @@ SIGNATURES = {
     "stormck_get_host": (
         c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
                 c_void_p, c_uint32, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64, POINTER(GetReportStruct), c_uint32]),
+    "stormck_update_workspace_bytes": (c_uint64, [c_uint64, c_uint32]),
+    "stormck_update_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
+                c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64,
+                POINTER(UpdateReportStruct), c_void_p]),
+    "stormck_update_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
+                c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, POINTER(UpdateReportStruct),
+                c_uint32]),
     "stormck_fill_synthetic_device": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p]),
 }
 

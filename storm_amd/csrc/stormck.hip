@@ -17,6 +17,7 @@
 #include <thread>
 #include <type_traits>
 #include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <dlfcn.h>
@@ -38,6 +39,7 @@
 #include "space_probe.h"
 #include "objlist_probe.h"
 #include "route_plan.h"
+#include "update_plan.h"
 #include "xxh64_host.h"
 
 using namespace stormck;
@@ -3008,6 +3010,7 @@ namespace {
 #include "objects.h"
 #include "spaces.h"
 #include "get.h"
+#include "update.h"
 
 }  // namespace
 
@@ -3093,6 +3096,28 @@ int stormck_get_host(const void* store, const stormck_scrub_layout* layout, uint
                      void* objects, uint64_t out_stride, stormck_get_report* report, uint32_t host_threads) {
     return get_host(store, layout, space_id, params, keys, stride, offsets, lens, len, n, flags, results, objects,
                     out_stride, report, host_threads);
+}
+
+uint64_t stormck_update_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block) {
+    return update_workspace_bytes(n_keys, chunks_per_block);
+}
+
+int stormck_update_device(void* d_store, const stormck_scrub_layout* layout, uint64_t space_id,
+                          const stormck_get_params* params, const void* d_keys, uint64_t stride, const uint64_t* d_offsets,
+                          const uint32_t* d_lens, uint32_t len, uint64_t n, const void* d_objects, uint64_t in_stride,
+                          uint32_t flags, stormck_update_result* d_results, void* d_workspace, uint64_t workspace_bytes,
+                          stormck_update_report* report, void* stream) {
+    return update_device(d_store, layout, space_id, params, d_keys, stride, d_offsets, d_lens, len, n, d_objects, in_stride,
+                         flags, d_results, d_workspace, workspace_bytes, report, stream);
+}
+
+int stormck_update_host(void* store, const stormck_scrub_layout* layout, uint64_t space_id,
+                        const stormck_get_params* params, const void* keys, uint64_t stride, const uint64_t* offsets,
+                        const uint32_t* lens, uint32_t len, uint64_t n, const void* objects, uint64_t in_stride,
+                        uint32_t flags, stormck_update_result* results, stormck_update_report* report,
+                        uint32_t host_threads) {
+    return update_host(store, layout, space_id, params, keys, stride, offsets, lens, len, n, objects, in_stride, flags,
+                       results, report, host_threads);
 }
 
 }  // extern "C"

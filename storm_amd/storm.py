@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib, keystore, spacestore, trace
-from ._lib import GetParamsStruct, GetReportStruct, GetResultStruct, lib
+from ._lib import GetParamsStruct, GetReportStruct, GetResultStruct, UpdateReportStruct, UpdateResultStruct, lib
 from .keystore import _addressing
 from .objectstore import BlobParams
 from .scrub import ScrubLayout
@@ -158,3 +158,119 @@ def get_host(buffer, layout: ScrubLayout, space_id: int, params: GetParams, keys
                               objects.ctypes.data if objects is not None and n else None, out_stride, ctypes.byref(raw),
                               threads)
     return results, objects, _report(rc, raw)
+
+
+# ---- update: storm.Set for keys that already have an object ----------------------------------
+
+UPDATE_NONE, UPDATE_WRITTEN, UPDATE_SUPERSEDED = 0, 1, 2
+UPDATE_RESULT_DTYPE = np.dtype([("object_id", "<u8"), ("key_address", "<u8"), ("object_address", "<u8"),
+                                ("index", "<u4"), ("stage", "u1"), ("status", "u1"), ("action", "u1"), ("reserved", "u1")])
+assert UPDATE_RESULT_DTYPE.itemsize == ctypes.sizeof(UpdateResultStruct) == 32
+
+
+class UpdateReport:
+    """stormck_update_report: ``get`` is the :class:`GetReport` of the get the call ran."""
+
+    FIELDS = ("n_written", "n_superseded", "n_dirty", "bytes_copied", "bytes_hashed", "revision", "last_allocated",
+              "first_new", "heights")
+
+    def __init__(self, raw: UpdateReportStruct, code: int, message: str):
+        self.get = GetReport(raw.get, _lib.OK, "")
+        self.n_written, self.n_superseded = int(raw.n_written), int(raw.n_superseded)
+        self.n_dirty = tuple(int(v) for v in raw.n_dirty)
+        self.bytes_copied, self.bytes_hashed = int(raw.bytes_copied), int(raw.bytes_hashed)
+        self.revision, self.last_allocated = int(raw.revision), int(raw.last_allocated)
+        self.first_new, self.heights = int(raw.first_new), int(raw.heights)
+        self.code = code          # STORMCK_OK, STORMCK_EMISMATCH or STORMCK_ENOSPC
+        self.message = message    # the get's text for its first bad key, or the room check's ("" when there is none)
+
+    @property
+    def ok(self) -> bool:
+        return self.code == _lib.OK
+
+    def as_dict(self) -> dict:
+        return dict({f: getattr(self, f) for f in self.FIELDS}, get=self.get.as_dict())
+
+    def __repr__(self) -> str:
+        return f"UpdateReport({self.as_dict()})"
+
+
+def update_workspace_bytes(n_keys: int, chunks_per_block: int) -> int:
+    return int(lib.stormck_update_workspace_bytes(n_keys, chunks_per_block))
+
+
+def update_results_numpy(results) -> np.ndarray:
+    """A device call's results as UPDATE_RESULT_DTYPE records on the host."""
+    return results.cpu().numpy().reshape(-1).view(UPDATE_RESULT_DTYPE)
+
+
+def _update_report(rc: int, raw: UpdateReportStruct) -> UpdateReport:
+    if rc not in (_lib.OK, _lib.EMISMATCH, _lib.ENOSPC):
+        _lib.check(rc)
+    return UpdateReport(raw, rc, _lib.last_error() if rc else "")
+
+
+def update_device(store, layout: ScrubLayout, space_id: int, params: GetParams, keys, objects, offsets=None, lens=None,
+                  length=None, stream: int = 0, workspace=None, flags: int = 0):
+    """Write row i of `objects` (a contiguous (n, in_stride) CUDA byte tensor, in_stride at least
+    object_size) over the object of key i in space `space_id` of the device-resident store `store`
+    (a CUDA tensor or a raw device pointer), which is changed in place: a new revision. Keys as in
+    ``get_device``. Returns when the store is written."""
+    import torch
+    if isinstance(store, torch.Tensor):
+        if not store.is_cuda or not store.is_contiguous():
+            raise ValueError("store must be a contiguous CUDA tensor")
+        if store.numel() * store.element_size() < layout.image_bytes():
+            raise ValueError("store tensor is smaller than n_blocks * block_size")
+        d_store, device = store.data_ptr(), store.device
+    else:
+        d_store, device = int(store), torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or not keys.is_contiguous() or keys.element_size() != 1:
+        raise ValueError("keys must be a contiguous CUDA byte tensor")
+    n, stride, length = _addressing(tuple(keys.shape), offsets, lens, length)
+    if (not isinstance(objects, torch.Tensor) or not objects.is_cuda or not objects.is_contiguous() or
+            objects.element_size() != 1 or objects.dim() != 2 or objects.shape[0] != n):
+        raise ValueError("objects must be a contiguous (n, in_stride) CUDA byte tensor")
+    need = update_workspace_bytes(n, params.keys.chunks_per_block)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
+    results = torch.empty((n, 4), dtype=torch.int64, device=device)
+    raw = UpdateReportStruct()
+    rc = lib.stormck_update_device(d_store, ctypes.byref(layout), int(space_id), ctypes.byref(params.raw), keys.data_ptr(),
+                                   stride, offsets.data_ptr() if offsets is not None else None,
+                                   lens.data_ptr() if lens is not None else None, length, n,
+                                   objects.data_ptr() if n else None, int(objects.shape[1]), flags, results.data_ptr(),
+                                   workspace.data_ptr(), workspace.numel() * workspace.element_size(), ctypes.byref(raw),
+                                   stream or None)
+    return results, _update_report(rc, raw)
+
+
+def update_host(buffer, layout: ScrubLayout, space_id: int, params: GetParams, keys, objects, offsets=None, lens=None,
+                length=None, threads: int = 0, flags: int = 0):
+    """The same over a store in host memory, changed in place: `buffer` is a writable, contiguous
+    uint8 numpy array (ValueError otherwise); `keys` and `objects` are uint8 numpy arrays. Needs no
+    device."""
+    if not isinstance(buffer, np.ndarray) or buffer.dtype != np.uint8 or not buffer.flags.c_contiguous:
+        raise ValueError("buffer must be a contiguous uint8 numpy array")
+    if not buffer.flags.writeable:
+        raise ValueError("buffer is read-only: the update writes the store in place")
+    buf = buffer.reshape(-1)
+    if buf.size < layout.image_bytes():
+        raise ValueError("buffer is smaller than n_blocks * block_size")
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, dtype=np.uint32).reshape(-1)
+    n, stride, length = _addressing(keys.shape, offsets, lens, length)
+    if (not isinstance(objects, np.ndarray) or objects.dtype != np.uint8 or not objects.flags.c_contiguous or
+            objects.ndim != 2 or objects.shape[0] != n):
+        raise ValueError("objects must be a contiguous (n, in_stride) uint8 array")
+    results = np.zeros(n, dtype=UPDATE_RESULT_DTYPE)
+    raw = UpdateReportStruct()
+    rc = lib.stormck_update_host(buf.ctypes.data, ctypes.byref(layout), int(space_id), ctypes.byref(params.raw),
+                                 keys.ctypes.data, stride, offsets.ctypes.data if offsets is not None else None,
+                                 lens.ctypes.data if lens is not None else None, length, n,
+                                 objects.ctypes.data if n else None, int(objects.shape[1]), flags,
+                                 results.ctypes.data if n else None, ctypes.byref(raw), threads)
+    return results, _update_report(rc, raw)
