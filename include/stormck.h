@@ -1094,6 +1094,155 @@ int stormck_update_host(void* store, const stormck_scrub_layout* layout, uint64_
                         uint32_t flags, stormck_update_result* results, stormck_update_report* report,
                         uint32_t host_threads);
 
+/* ---- insert: storm.Set for new keys whose leaves have room, as a new revision ------------
+ * On a key that is not in the store, storm.Set runs EnsureObjectID (keystore/keystore.go:48-110),
+ * which puts the key into its objectlist leaf under the space's NextObjectID, and SetObject
+ * (objectstore/objectstore.go:41-90), which puts the object into a slot of the ID's blob leaf.
+ * This is that case for n keys of one existing space in one call, in place in the image, for
+ * every key that storm would insert without a split and without allocating a leaf. The new
+ * store is what storm's serial loop over the accepted keys, in batch order, would leave, under
+ * the two deviations of "update" (a batch that changes nothing makes no revision; every dirty
+ * block moves). Every other key is NONE with a reason: the caller sends it to the update call
+ * (EXISTS) or to storm's own Set. Arguments as in "update"; flags must be 0.
+ * chunks_per_block is at most STORMCK_INSERT_MAX_CHUNKS (the device's leaf worker holds a leaf
+ * image and its ordering buffer in LDS), else STORMCK_EINVAL. n == 0 is a no-op with a zero report.
+ *
+ * A. Locate (nothing is written). The singularity's check as in "get", "spaces" with n = 1,
+ *    "lookup" over the keys from the space's key root with leaves verified. When a stage returns
+ *    STORMCK_EMISMATCH the call returns that code and text, every action is NONE with reason 0
+ *    and the store is byte for byte as it was. A space that is not FOUND: every key is NONE /
+ *    SPACE, STORMCK_OK, store untouched. Else a key whose lookup ended FOUND is NONE / EXISTS; one
+ *    whose trace ended at a Free reference (probes == 0, ABSENT) is NONE / NO_LEAF; one that was
+ *    probed and is ABSENT is a candidate.
+ * B. Key stage. Each objectlist leaf's candidates are taken in ascending key index, each judged
+ *    against the leaf as the earlier ones left it (keystore.go:72-109, literally):
+ *    1. findChunkPointerForKey with the key. A Defined match is a key an earlier candidate of the
+ *       batch put there: REPEATED, with object_id and key_index of that item.
+ *    2. Else NUsedChunks >= C * 3 / 4 (SplitTrigger): NONE / KEY_SPLIT.
+ *    3. Else no slot was handed out: NONE / NO_SLOT.
+ *    4. Else NUsedChunks + ceil(len / 32) > C: NONE / KEY_FULL.
+ *    5. Else setKeyInChunks byte for byte: initFreeChunkList when NUsedChunks == 0; state
+ *       Defined, ChunkPointers[index] = FreeChunkIndex, KeyTagReminders[index] = the reminder; the
+ *       chunks taken off the free list, each receiving only the key's bytes; the last next
+ *       pointer = C + nCopied; ObjectLinks[index] = the key's new ID: INSERTED. Before anything
+ *       changes the ceil(len / 32) steps of the free list are walked; a FreeChunkIndex or next
+ *       pointer >= C on the way (storm would index out of range) makes the key NONE / MALFORMED
+ *       with the leaf as it was before the key.
+ *    A leaf with more than STORMCK_INSERT_MAX_PER_LEAF candidates: all of them NONE / CROWDED. A
+ *    later, shorter key may be accepted after a KEY_FULL one.
+ * C. IDs. The INSERTED keys ranked in key order: rank r gets NextObjectID + r (keystore.go:104-105).
+ * D. Object stage (still nothing written). "objects" over the new IDs from the space's object
+ *    root, leaves verified; a MISMATCH, RANGE, TYPE or DEPTH there ends the call
+ *    STORMCK_EMISMATCH with the trace's text, every action NONE with reason 0, store untouched.
+ *    Each blob leaf's IDs are taken in ascending rank against the leaf's slots as the earlier
+ *    ones left them (objectstore.go:59-85, literally): findObject; a slot that is nil or not
+ *    Defined while NUsedSlots >= N * 3 / 4 fails the rank (storm splits); a nil slot fails it
+ *    (storm errors); a Defined slot with the ID's reminder (NextObjectID lags) is overwritten
+ *    without counting. A trace that ends at a Free reference fails (storm allocates). A leaf with
+ *    more than STORMCK_INSERT_MAX_PER_LEAF IDs fails at its smallest rank. cut = the smallest
+ *    failing rank, or the number of INSERTED keys.
+ * E. Cut. limit = the key index of the INSERTED key of rank cut (n if none). Every key i >= limit
+ *    becomes NONE / CUT with the fields the locate left; the verdicts below limit stand. With no
+ *    INSERTED key left: STORMCK_OK, store untouched, Revision included.
+ * F. Rows. The slot of an INSERTED key below limit receives the row of that key's last
+ *    occurrence below limit (itself or a REPEATED one); that occurrence has wrote = 1 once the
+ *    call has written (after STORMCK_ENOSPC no slot received anything and every wrote is 0).
+ * G. Dirty forest and plan. Dirty: the objectlist leaves with an INSERTED key and the key
+ *    tree's pointer blocks on those keys' walks; the blob leaves of the placed IDs and the object
+ *    tree's pointer blocks on their walks; the spacelist leaf and the space ID's path. Heights,
+ *    order, new addresses L + 1 + k and STORMCK_ENOSPC as rule C of "update". The spacelist leaf
+ *    has up to two dirty children: KeyStorePointer @72k+16 with its type @72k+64,
+ *    ObjectStorePointer @72k+40 with its type @72k+65.
+ * H. Write, everything above L, the singularity last. A key leaf's new copy is the old leaf with
+ *    its inserts; every other dirty block is copied. Blob slots: Object = the row; if the slot
+ *    was not Defined, NUsedSlots++, the reminder, state Defined. NextObjectID = old + cut @72k+8
+ *    in the spacelist leaf's new copy. Then the commit over the copies and the singularity's 72
+ *    bytes. The three consequences of "update" hold unchanged.
+ *
+ * The result of a key: object_id is the key's ID after the call for INSERTED / REPEATED, the ID
+ * it has for EXISTS, else 0. key_address: the lookup's final address. key_index: the item for
+ * INSERTED / REPEATED / EXISTS, else the slot the lookup found free (or NO_SLOT). object_address
+ * (on the old store) and object_index: the blob leaf and slot of an INSERTED key, else 0 and
+ * NO_SLOT. stage / status: 0 and the space's status when the space is not FOUND; 2 and the object
+ * stage's (ABSENT, or FOUND for a lagging NextObjectID) for an INSERTED key; else 1 and the
+ * lookup's. */
+#define STORMCK_HAS_INSERT 1
+#define STORMCK_INSERT_MAX_CHUNKS 1024
+#define STORMCK_INSERT_MAX_PER_LEAF 2048
+enum { STORMCK_INSERT_NONE = 0, STORMCK_INSERT_INSERTED = 1, STORMCK_INSERT_REPEATED = 2 };
+enum {
+    STORMCK_INSERT_R_NONE = 0,  /* INSERTED, REPEATED, or a call that returned STORMCK_EMISMATCH */
+    STORMCK_INSERT_R_SPACE = 1, STORMCK_INSERT_R_EXISTS = 2, STORMCK_INSERT_R_NO_LEAF = 3, STORMCK_INSERT_R_KEY_SPLIT = 4,
+    STORMCK_INSERT_R_NO_SLOT = 5, STORMCK_INSERT_R_KEY_FULL = 6, STORMCK_INSERT_R_MALFORMED = 7,
+    STORMCK_INSERT_R_CROWDED = 8, STORMCK_INSERT_R_CUT = 9, STORMCK_INSERT_REASONS = 10
+};
+typedef struct stormck_insert_result {  /* 40 bytes */
+    uint64_t object_id;
+    uint64_t key_address;
+    uint64_t object_address;  /* on the old store */
+    uint32_t key_index;
+    uint32_t object_index;
+    uint8_t stage, status;
+    uint8_t action;           /* STORMCK_INSERT_NONE / INSERTED / REPEATED */
+    uint8_t reason;           /* STORMCK_INSERT_R_* */
+    uint8_t wrote;            /* this key's row is the one its slot received */
+    uint8_t reserved[3];
+} stormck_insert_result;
+typedef struct stormck_insert_report {
+    stormck_space_result space;    /* the one space's result (zeros when the singularity failed) */
+    stormck_lookup_report lookup;  /* of the lookup the call ran, unchanged (zeros, first_bad n, when it did not run) */
+    uint64_t n_inserted, n_repeated;
+    uint64_t n_none[STORMCK_INSERT_REASONS];  /* NONE keys per reason */
+    uint64_t first_id;               /* NextObjectID before the call; 0 when the space is not FOUND */
+    uint64_t next_object_id;         /* ... after it: first_id + cut when something was written, else first_id */
+    uint64_t cut, limit;             /* rule E; 0 and n when the key stage did not run */
+    uint64_t n_dirty[4];             /* dirty blocks per STORMCK_SCRUB_* kind */
+    uint64_t bytes_copied;           /* D * block_size */
+    uint64_t bytes_hashed;           /* of the dirty blocks at their kinds' lengths, and the singularity's 72 */
+    uint64_t revision;               /* the singularity's after the call, when the locate returned STORMCK_OK; otherwise 0 */
+    uint64_t last_allocated;         /* likewise */
+    uint64_t first_new;              /* L + 1, or 0 when nothing moved */
+    uint32_t heights, reserved;      /* distinct heights of the dirty forest */
+} stormck_insert_report;
+
+/* Bytes of device workspace a call with n_keys needs, with m = (n_keys + 7) & ~7 and T = the
+ * smallest power of two that is at least 64 and at least 2 * n_keys:
+ *   max(stormck_lookup_workspace_bytes(n_keys, C), stormck_spaces_workspace_bytes(1, 32768),
+ *       stormck_objects_workspace_bytes(n_keys)) rounded up to 8: the part the three engines use in turn
+ * + 32 m (the lookup's results) + 8 m (the keys' tags) + 8 m (the new IDs) + 32 m (the object
+ *   stage's results) + 4 m (each key's rank) + 4 m (each rank's key) + 4 m (each key's last occurrence)
+ * + 8 m (each item's leaf, for the grouping) + 2 * 4 m (the segments of the key leaves and of the
+ *   blob leaves) + 3 * 8 (m + 8) (the addresses of the key leaves and of the blob leaves, and the
+ *   key leaves' new addresses) + 3 * 4 (m + 8) (the two groupings' counts, then starts, and the
+ *   fill's cursors)
+ * + 8 (n_keys / 256 + 2) (the compaction's counts) + 12 T (the table of distinct leaves and
+ *   blocks) + 24 (m + 72) (the dirty blocks of one tree level, and the space's path)
+ * + ((2 C + 7) & ~7) (the addressing table) + 128 (the space) + 64 + 128 (the counters):
+ * O(n_keys), whatever the image's size. Host logic. */
+uint64_t stormck_insert_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block);
+/* Insert the n keys (addressed as in stormck_lookup_device) with their rows (as in "update")
+ * into space space_id of the device-resident store d_store, which is written in place. Steps on
+ * `stream`: the three engines; the grouping of the candidates by leaf (a table, a scan, a fill);
+ * k_insert_keys with one workgroup per key leaf on an LDS image of the leaf; the ranks; the
+ * objects call over the new IDs; the grouping by blob leaf and k_insert_slots with one wave per
+ * leaf; the dirty walks, one tree level per launch; the plan on the host; k_update_copy,
+ * k_insert_keys and k_insert_slots again, now writing the new copies; the device commit; the
+ * singularity's 72 bytes. Synchronous. STORMCK_EINVAL, before any work, as "update", and for
+ * chunks_per_block above STORMCK_INSERT_MAX_CHUNKS. */
+int stormck_insert_device(void* d_store, const stormck_scrub_layout* layout, uint64_t space_id,
+                          const stormck_get_params* params, const void* d_keys, uint64_t stride, const uint64_t* d_offsets,
+                          const uint32_t* d_lens, uint32_t len, uint64_t n, const void* d_objects, uint64_t in_stride,
+                          uint32_t flags, stormck_insert_result* d_results, void* d_workspace, uint64_t workspace_bytes,
+                          stormck_insert_report* report, void* stream);
+/* The same over a store in host memory with host pointers throughout: plain loops over the same
+ * rule functions; the library's pool works only inside the lookup, the trace and the commit.
+ * Same rules, results, image bytes, report and return codes; needs no device and no workspace. */
+int stormck_insert_host(void* store, const stormck_scrub_layout* layout, uint64_t space_id,
+                        const stormck_get_params* params, const void* keys, uint64_t stride, const uint64_t* offsets,
+                        const uint32_t* lens, uint32_t len, uint64_t n, const void* objects, uint64_t in_stride,
+                        uint32_t flags, stormck_insert_result* results, stormck_insert_report* report,
+                        uint32_t host_threads);
+
 /* ---- synthetic data (benchmarks / tests) -----------------------------------
  * Word w of block i = splitmix64(seed ^ (((first + i) << 20) + w)), w < stride/8,
  * little-endian. stride % 16 == 0, d_dst 16-byte aligned. */

@@ -197,6 +197,27 @@ class UpdateReportStruct(ctypes.Structure):
                 ("last_allocated", c_uint64), ("first_new", c_uint64), ("heights", c_uint32), ("reserved", c_uint32)]
 
 
+class InsertResultStruct(ctypes.Structure):
+    """stormck_insert_result: what the insert did with one key (40 bytes)."""
+
+    _fields_ = [("object_id", c_uint64), ("key_address", c_uint64), ("object_address", c_uint64), ("key_index", c_uint32),
+                ("object_index", c_uint32), ("stage", c_uint8), ("status", c_uint8), ("action", c_uint8),
+                ("reason", c_uint8), ("wrote", c_uint8), ("reserved", c_uint8 * 3)]
+
+
+INSERT_REASONS = 10
+
+
+class InsertReportStruct(ctypes.Structure):
+    """stormck_insert_report."""
+
+    _fields_ = [("space", SpaceResultStruct), ("lookup", LookupReportStruct), ("n_inserted", c_uint64),
+                ("n_repeated", c_uint64), ("n_none", c_uint64 * INSERT_REASONS), ("first_id", c_uint64),
+                ("next_object_id", c_uint64), ("cut", c_uint64), ("limit", c_uint64), ("n_dirty", c_uint64 * 4),
+                ("bytes_copied", c_uint64), ("bytes_hashed", c_uint64), ("revision", c_uint64),
+                ("last_allocated", c_uint64), ("first_new", c_uint64), ("heights", c_uint32), ("reserved", c_uint32)]
+
+
 # name -> (restype, argtypes); mirrors include/stormck.h one to one.
 SIGNATURES = {
     "stormck_abi_version": (c_int, []),
@@ -326,6 +347,15 @@ SIGNATURES = {
     "stormck_update_host": (
         c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
                 c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, POINTER(UpdateReportStruct),
+                c_uint32]),
+    "stormck_insert_workspace_bytes": (c_uint64, [c_uint64, c_uint32]),
+    "stormck_insert_device": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
+                c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, c_void_p, c_uint64,
+                POINTER(InsertReportStruct), c_void_p]),
+    "stormck_insert_host": (
+        c_int, [c_void_p, POINTER(ScrubLayoutStruct), c_uint64, POINTER(GetParamsStruct), c_void_p, c_uint64, c_void_p,
+                c_void_p, c_uint32, c_uint64, c_void_p, c_uint64, c_uint32, c_void_p, POINTER(InsertReportStruct),
                 c_uint32]),
     "stormck_fill_synthetic_device": (c_int, [c_void_p, c_uint64, c_uint64, c_uint64, c_uint64, c_void_p]),
 }

@@ -35,7 +35,7 @@ def _newer(target: str, sources) -> bool:
 
 
 # the sources libstormck.so is compiled from (its build id hashes them)
-SOURCES = [os.path.join(CSRC, f) for f in ("stormck.hip", "commit_plan.h", "dispatch.h", "kernels.h", "route_plan.h", "multi_root.h", "scrub.h", "trace.h", "lookup.h", "objlist_probe.h", "objects.h", "blob_probe.h", "spaces.h", "space_probe.h", "get.h", "update.h", "update_plan.h", "xxh64_dev.h", "xxh64_host.h")] + \
+SOURCES = [os.path.join(CSRC, f) for f in ("stormck.hip", "commit_plan.h", "dispatch.h", "kernels.h", "route_plan.h", "multi_root.h", "scrub.h", "trace.h", "lookup.h", "objlist_probe.h", "objects.h", "blob_probe.h", "spaces.h", "space_probe.h", "get.h", "update.h", "update_plan.h", "insert.h", "objlist_insert.h", "blob_insert.h", "xxh64_dev.h", "xxh64_host.h")] + \
     [os.path.join(ROOT, "include", "stormck.h")]
 
 

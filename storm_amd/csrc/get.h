@@ -181,11 +181,19 @@ int get_host(const void* store, const stormck_scrub_layout* layout, uint64_t spa
 
 // ---- device engine ------------------------------------------------------------------------
 
-// Keys that were FOUND, per workgroup of 256 keys.
-__global__ void __launch_bounds__(256) k_get_count(const stormck_lookup_result* __restrict__ L, uint64_t n,
-                                                   uint32_t* __restrict__ counts) {
+// Which items the compaction keeps, and the ID of a kept item at its place: the get's are the keys
+// whose lookup ended FOUND, with their object IDs.
+struct GetPick {
+    const stormck_lookup_result* L;
+    __device__ bool operator()(uint64_t i) const { return L[i].status == STORMCK_TRACE_FOUND; }
+    __device__ uint64_t id(uint64_t i, uint32_t) const { return L[i].object_id; }
+};
+
+// Items that `pick` keeps (the get: keys that were FOUND), per workgroup of 256 items.
+template <class Pick>
+__global__ void __launch_bounds__(256) k_get_count(Pick pick, uint64_t n, uint32_t* __restrict__ counts) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-    const int c = __syncthreads_count(i < n && L[i].status == STORMCK_TRACE_FOUND);
+    const int c = __syncthreads_count(i < n && pick(i));
     if (threadIdx.x == 0) counts[blockIdx.x] = static_cast<uint32_t>(c);
 }
 
@@ -210,15 +218,17 @@ __global__ void __launch_bounds__(256) k_get_scan(uint32_t* counts, uint64_t nb)
     }
 }
 
-// Each FOUND key's place among the FOUND keys, in key order: its object ID goes there (ids), the
-// key remembers the place (pos, kGetNone for every other key) and the place the key (key_of).
-__global__ void __launch_bounds__(256) k_get_select(const stormck_lookup_result* __restrict__ L, uint64_t n,
-                                                    const uint32_t* __restrict__ counts, uint64_t* __restrict__ ids,
-                                                    uint32_t* __restrict__ pos, uint32_t* __restrict__ key_of) {
+// Each kept item's place among the kept items, in item order (the get: each FOUND key's among the
+// FOUND keys): its ID goes there (ids), the item remembers the place (pos, kGetNone for every other
+// item) and the place the item (key_of).
+template <class Pick>
+__global__ void __launch_bounds__(256) k_get_select(Pick pick, uint64_t n, const uint32_t* __restrict__ counts,
+                                                    uint64_t* __restrict__ ids, uint32_t* __restrict__ pos,
+                                                    uint32_t* __restrict__ key_of) {
     __shared__ uint32_t waves[4];
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
-    const bool found = i < n && L[i].status == STORMCK_TRACE_FOUND;
+    const bool found = i < n && pick(i);
     const unsigned long long m = __ballot(found);
     if (lane == 0) waves[wave] = static_cast<uint32_t>(__popcll(m));
     __syncthreads();
@@ -226,7 +236,7 @@ __global__ void __launch_bounds__(256) k_get_select(const stormck_lookup_result*
     for (uint32_t w = 0; w < wave; ++w) at += waves[w];
     if (i < n) pos[i] = found ? at : kGetNone;
     if (found) {
-        ids[at] = L[i].object_id;
+        ids[at] = pick.id(i, at);
         key_of[at] = static_cast<uint32_t>(i);  // n <= 2^31
     }
 }
@@ -340,11 +350,11 @@ int get_device(const void* d_store, const stormck_scrub_layout* layout, uint64_t
     if (rc != STORMCK_OK && rc != STORMCK_EMISMATCH) return rc;
     const std::string lookup_text = rc ? g_last_error : std::string();
     const uint64_t n_sel = report->lookup.n_status[STORMCK_TRACE_FOUND];
-    hipLaunchKernelGGL(k_get_count, dim3(wgs), dim3(256), 0, st, L, n, counts);
+    hipLaunchKernelGGL(k_get_count<GetPick>, dim3(wgs), dim3(256), 0, st, GetPick{L}, n, counts);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_get_scan, dim3(1), dim3(256), 0, st, counts, static_cast<uint64_t>(wgs));
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_get_select, dim3(wgs), dim3(256), 0, st, L, n, counts, ids, pos, key_of);
+    hipLaunchKernelGGL(k_get_select<GetPick>, dim3(wgs), dim3(256), 0, st, GetPick{L}, n, counts, ids, pos, key_of);
     HIP_TRY(hipGetLastError());
     stormck_objects_report orep;
     rc = objects_device(d_store, layout, &report->space.object_root, report->space.object_type, &params->objects, ids, 8,

@@ -40,6 +40,8 @@
 #include "objlist_probe.h"
 #include "route_plan.h"
 #include "update_plan.h"
+#include "objlist_insert.h"
+#include "blob_insert.h"
 #include "xxh64_host.h"
 
 using namespace stormck;
@@ -3011,6 +3013,7 @@ namespace {
 #include "spaces.h"
 #include "get.h"
 #include "update.h"
+#include "insert.h"
 
 }  // namespace
 
@@ -3117,6 +3120,28 @@ int stormck_update_host(void* store, const stormck_scrub_layout* layout, uint64_
                         uint32_t flags, stormck_update_result* results, stormck_update_report* report,
                         uint32_t host_threads) {
     return update_host(store, layout, space_id, params, keys, stride, offsets, lens, len, n, objects, in_stride, flags,
+                       results, report, host_threads);
+}
+
+uint64_t stormck_insert_workspace_bytes(uint64_t n_keys, uint32_t chunks_per_block) {
+    return insert_workspace_bytes(n_keys, chunks_per_block);
+}
+
+int stormck_insert_device(void* d_store, const stormck_scrub_layout* layout, uint64_t space_id,
+                          const stormck_get_params* params, const void* d_keys, uint64_t stride, const uint64_t* d_offsets,
+                          const uint32_t* d_lens, uint32_t len, uint64_t n, const void* d_objects, uint64_t in_stride,
+                          uint32_t flags, stormck_insert_result* d_results, void* d_workspace, uint64_t workspace_bytes,
+                          stormck_insert_report* report, void* stream) {
+    return insert_device(d_store, layout, space_id, params, d_keys, stride, d_offsets, d_lens, len, n, d_objects, in_stride,
+                         flags, d_results, d_workspace, workspace_bytes, report, stream);
+}
+
+int stormck_insert_host(void* store, const stormck_scrub_layout* layout, uint64_t space_id,
+                        const stormck_get_params* params, const void* keys, uint64_t stride, const uint64_t* offsets,
+                        const uint32_t* lens, uint32_t len, uint64_t n, const void* objects, uint64_t in_stride,
+                        uint32_t flags, stormck_insert_result* results, stormck_insert_report* report,
+                        uint32_t host_threads) {
+    return insert_host(store, layout, space_id, params, keys, stride, offsets, lens, len, n, objects, in_stride, flags,
                        results, report, host_threads);
 }
 

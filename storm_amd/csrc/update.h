@@ -316,20 +316,34 @@ __global__ void __launch_bounds__(64) k_update_space_walk(const uint8_t* __restr
     C->space_count = count;
 }
 
-// One lane per WRITTEN key: the block at `depth` on its object ID's walk from the object root
-// (the blocks were verified by the get: nothing is hashed). The lane that installs the block in
-// the table, which the host clears per level, appends its record; a wave claims its records with
-// one atomicAdd. A lane whose block is a pointer block says that a deeper level exists.
-__global__ void __launch_bounds__(256) k_update_walk(const uint8_t* __restrict__ base, UpdateGeometry G,
-                                                     const stormck_update_result* __restrict__ results, uint64_t n,
-                                                     UpdateStep root, uint32_t depth, UpdateTable T,
-                                                     UpdateDirty* __restrict__ records, uint64_t cap, UpdateCounters* C) {
+// Which items a walk follows, and the tag of each: the update's are its WRITTEN keys with their
+// object IDs.
+struct UpdatePick {
+    const stormck_update_result* results;
+    __device__ bool operator()(uint64_t i, uint64_t* tag) const {
+        if (results[i].action != STORMCK_UPDATE_WRITTEN) return false;
+        *tag = results[i].object_id;
+        return true;
+    }
+};
+
+// One lane per item that `pick` takes (the update: per WRITTEN key): the block at `depth` on its
+// tag's walk from `root` (the update: its object ID's, from the object root; the blocks were
+// verified before: nothing is hashed). The lane that installs the block in the table, which the
+// host clears per level, appends its record, a leaf's with `leaf_kind`; a wave claims its records
+// with one atomicAdd. A lane whose block is a pointer block says that a deeper level exists.
+template <class Pick>
+__global__ void __launch_bounds__(256) k_update_walk(const uint8_t* __restrict__ base, UpdateGeometry G, Pick pick,
+                                                     uint64_t n, UpdateStep root, uint32_t depth, uint32_t leaf_kind,
+                                                     UpdateTable T, UpdateDirty* __restrict__ records, uint64_t cap,
+                                                     UpdateCounters* C) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256 + threadIdx.x;
     const uint32_t lane = threadIdx.x & 63;
     bool here = false, owner = false, deeper = false;  // no early return: the wave votes below
     UpdateStep s = root;
-    if (i < n && results[i].action == STORMCK_UPDATE_WRITTEN) {
-        s.rem = results[i].object_id;
+    uint64_t tag = 0;
+    if (i < n && pick(i, &tag)) {
+        s.rem = tag;
         here = true;
         for (uint32_t d = 0; d < depth && here; ++d) {
             if (!update_step_ok(s, G.n_blocks)) {
@@ -359,7 +373,7 @@ __global__ void __launch_bounds__(256) k_update_walk(const uint8_t* __restrict__
         if (owner) {
             if (idx < cap)  // always: a level has at most as many distinct blocks as WRITTEN keys
                 records[idx] = UpdateDirty{s.address, s.parent, s.slot,
-                                           deeper ? uint32_t{STORMCK_SCRUB_POINTER} : uint32_t{STORMCK_SCRUB_BLOB}};
+                                           deeper ? uint32_t{STORMCK_SCRUB_POINTER} : leaf_kind};
             else
                 atomicOr(&C->error, 16ULL);
         }
@@ -548,8 +562,8 @@ int update_device(void* d_store, const stormck_scrub_layout* layout, uint64_t sp
         if (depth > kUpdateMaxDepth) return fail(STORMCK_EHIP, "update: a walk left the path the get verified");
         HIP_TRY(hipMemsetAsync(T.keys, 0xff, 8 * slots, st));
         HIP_TRY(hipMemsetAsync(&C->count, 0, 16, st));  // count and alive
-        hipLaunchKernelGGL(k_update_walk, dim3(wgs), dim3(256), 0, st, base, G, d_results, n, object_root, depth, T, records,
-                           m, C);
+        hipLaunchKernelGGL(k_update_walk<UpdatePick>, dim3(wgs), dim3(256), 0, st, base, G, UpdatePick{d_results}, n,
+                           object_root, depth, uint32_t{STORMCK_SCRUB_BLOB}, T, records, m, C);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(&h, C, sizeof h, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));

@@ -16,7 +16,11 @@ namespace stormck {
 
 // One dirty block as the walks find it. parent: the old address of the dirty block that holds
 // its origin, 0 for the topmost block (its origin is the singularity). slot: the entry of a
-// pointer block, the space's index k of a spacelist leaf.
+// pointer block, the space's index k of a spacelist leaf. A spacelist leaf holds two origins per
+// space: a child says with kUpdateKeyOrigin in `slot` that its own is the KeyStorePointer; without
+// it (every child of an update) it is the ObjectStorePointer.
+constexpr uint32_t kUpdateKeyOrigin = 1u << 31;
+
 struct UpdateDirty {
     uint64_t address, parent;
     uint32_t slot, kind;  // STORMCK_SCRUB_*
@@ -46,10 +50,12 @@ inline const char* update_error_message(UpdateError e) {
 
 // Where the parent's copy of `kind` at arena offset `at` keeps entry `slot`'s Pointer and type.
 inline uint64_t update_origin_pointer(uint64_t at, uint32_t kind, uint32_t slot) {
-    return at + (kind == STORMCK_SCRUB_POINTER ? 24ull * slot : 72ull * slot + 40);
+    if (kind == STORMCK_SCRUB_POINTER) return at + 24ull * slot;
+    return at + 72ull * (slot & ~kUpdateKeyOrigin) + ((slot & kUpdateKeyOrigin) ? 16 : 40);
 }
 inline uint64_t update_origin_type(uint64_t at, uint32_t kind, uint32_t slot, uint32_t fanout) {
-    return at + (kind == STORMCK_SCRUB_POINTER ? 24ull * fanout + slot : 72ull * slot + 65);
+    if (kind == STORMCK_SCRUB_POINTER) return at + 24ull * fanout + slot;
+    return at + 72ull * (slot & ~kUpdateKeyOrigin) + ((slot & kUpdateKeyOrigin) ? 64 : 65);
 }
 
 struct UpdatePlan {

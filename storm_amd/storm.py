@@ -20,7 +20,8 @@ import ctypes
 import numpy as np
 
 from . import _lib, keystore, spacestore, trace
-from ._lib import GetParamsStruct, GetReportStruct, GetResultStruct, UpdateReportStruct, UpdateResultStruct, lib
+from ._lib import (GetParamsStruct, GetReportStruct, GetResultStruct, InsertReportStruct, InsertResultStruct,
+                   UpdateReportStruct, UpdateResultStruct, lib)
 from .keystore import _addressing
 from .objectstore import BlobParams
 from .scrub import ScrubLayout
@@ -274,3 +275,124 @@ def update_host(buffer, layout: ScrubLayout, space_id: int, params: GetParams, k
                                  objects.ctypes.data if n else None, int(objects.shape[1]), flags,
                                  results.ctypes.data if n else None, ctypes.byref(raw), threads)
     return results, _update_report(rc, raw)
+
+
+# ---- insert: storm.Set for new keys whose leaves have room ------------------------------------
+
+INSERT_NONE, INSERT_INSERTED, INSERT_REPEATED = 0, 1, 2
+(R_NONE, R_SPACE, R_EXISTS, R_NO_LEAF, R_KEY_SPLIT, R_NO_SLOT, R_KEY_FULL, R_MALFORMED, R_CROWDED,
+ R_CUT) = range(_lib.INSERT_REASONS)
+INSERT_MAX_CHUNKS, INSERT_MAX_PER_LEAF = 1024, 2048
+INSERT_RESULT_DTYPE = np.dtype([("object_id", "<u8"), ("key_address", "<u8"), ("object_address", "<u8"),
+                                ("key_index", "<u4"), ("object_index", "<u4"), ("stage", "u1"), ("status", "u1"),
+                                ("action", "u1"), ("reason", "u1"), ("wrote", "u1"), ("reserved", "u1", (3,))])
+assert INSERT_RESULT_DTYPE.itemsize == ctypes.sizeof(InsertResultStruct) == 40
+
+
+class InsertReport:
+    """stormck_insert_report: ``space`` is the space's record, ``lookup`` the lookup's report."""
+
+    FIELDS = ("n_inserted", "n_repeated", "n_none", "first_id", "next_object_id", "cut", "limit", "n_dirty",
+              "bytes_copied", "bytes_hashed", "revision", "last_allocated", "first_new", "heights")
+
+    def __init__(self, raw: InsertReportStruct, code: int, message: str):
+        self.space = np.frombuffer(bytes(raw.space), dtype=spacestore.RESULT_DTYPE)[0]
+        self.lookup = keystore.LookupReport(raw.lookup, _lib.OK, "")
+        for f in self.FIELDS:
+            v = getattr(raw, f)
+            setattr(self, f, int(v) if isinstance(v, int) else tuple(int(x) for x in v))
+        self.code = code          # STORMCK_OK, STORMCK_EMISMATCH or STORMCK_ENOSPC
+        self.message = message    # the failing stage's text, or the room check's ("" when there is none)
+
+    @property
+    def ok(self) -> bool:
+        return self.code == _lib.OK
+
+    def as_dict(self) -> dict:
+        return dict({f: getattr(self, f) for f in self.FIELDS}, lookup=self.lookup.as_dict(), space=self.space.tobytes())
+
+    def __repr__(self) -> str:
+        return f"InsertReport({self.as_dict()})"
+
+
+def insert_workspace_bytes(n_keys: int, chunks_per_block: int) -> int:
+    return int(lib.stormck_insert_workspace_bytes(n_keys, chunks_per_block))
+
+
+def insert_results_numpy(results) -> np.ndarray:
+    """A device call's results as INSERT_RESULT_DTYPE records on the host."""
+    return results.cpu().numpy().reshape(-1).view(INSERT_RESULT_DTYPE)
+
+
+def _insert_report(rc: int, raw: InsertReportStruct) -> InsertReport:
+    if rc not in (_lib.OK, _lib.EMISMATCH, _lib.ENOSPC):
+        _lib.check(rc)
+    return InsertReport(raw, rc, _lib.last_error() if rc else "")
+
+
+def insert_device(store, layout: ScrubLayout, space_id: int, params: GetParams, keys, objects, offsets=None, lens=None,
+                  length=None, stream: int = 0, workspace=None, flags: int = 0):
+    """Insert key i with row i of `objects` (a contiguous (n, in_stride) CUDA byte tensor) into space
+    `space_id` of the device-resident store `store`, which is changed in place: a new revision that
+    holds every key storm would insert without a split and without a new leaf. Keys as in
+    ``get_device``. Synchronous. Returns ``(results, report)``: an int64 tensor of shape (n, 5) that
+    ``insert_results_numpy`` views as INSERT_RESULT_DTYPE records, and an :class:`InsertReport`;
+    both come back whether or not anything was written."""
+    import torch
+    if isinstance(store, torch.Tensor):
+        if not store.is_cuda or not store.is_contiguous():
+            raise ValueError("store must be a contiguous CUDA tensor")
+        if store.numel() * store.element_size() < layout.image_bytes():
+            raise ValueError("store tensor is smaller than n_blocks * block_size")
+        d_store, device = store.data_ptr(), store.device
+    else:
+        d_store, device = int(store), torch.device("cuda", torch.cuda.current_device())
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or not keys.is_contiguous() or keys.element_size() != 1:
+        raise ValueError("keys must be a contiguous CUDA byte tensor")
+    n, stride, length = _addressing(tuple(keys.shape), offsets, lens, length)
+    if (not isinstance(objects, torch.Tensor) or not objects.is_cuda or not objects.is_contiguous() or
+            objects.element_size() != 1 or objects.dim() != 2 or objects.shape[0] != n):
+        raise ValueError("objects must be a contiguous (n, in_stride) CUDA byte tensor")
+    if workspace is None:
+        need = insert_workspace_bytes(n, params.keys.chunks_per_block)
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
+    results = torch.empty((n, 5), dtype=torch.int64, device=device)
+    raw = InsertReportStruct()
+    rc = lib.stormck_insert_device(d_store, ctypes.byref(layout), int(space_id), ctypes.byref(params.raw), keys.data_ptr(),
+                                   stride, offsets.data_ptr() if offsets is not None else None,
+                                   lens.data_ptr() if lens is not None else None, length, n,
+                                   objects.data_ptr() if n else None, int(objects.shape[1]), flags, results.data_ptr(),
+                                   workspace.data_ptr(), workspace.numel() * workspace.element_size(), ctypes.byref(raw),
+                                   stream or None)
+    return results, _insert_report(rc, raw)
+
+
+def insert_host(buffer, layout: ScrubLayout, space_id: int, params: GetParams, keys, objects, offsets=None, lens=None,
+                length=None, threads: int = 0, flags: int = 0):
+    """The same over a store in host memory, changed in place: `buffer` is a writable, contiguous
+    uint8 numpy array (ValueError otherwise); `keys` and `objects` are uint8 numpy arrays. Needs no
+    device."""
+    if not isinstance(buffer, np.ndarray) or buffer.dtype != np.uint8 or not buffer.flags.c_contiguous:
+        raise ValueError("buffer must be a contiguous uint8 numpy array")
+    if not buffer.flags.writeable:
+        raise ValueError("buffer is read-only: the insert writes the store in place")
+    buf = buffer.reshape(-1)
+    if buf.size < layout.image_bytes():
+        raise ValueError("buffer is smaller than n_blocks * block_size")
+    keys = np.ascontiguousarray(keys, dtype=np.uint8)
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+    if lens is not None:
+        lens = np.ascontiguousarray(lens, dtype=np.uint32).reshape(-1)
+    n, stride, length = _addressing(keys.shape, offsets, lens, length)
+    if (not isinstance(objects, np.ndarray) or objects.dtype != np.uint8 or not objects.flags.c_contiguous or
+            objects.ndim != 2 or objects.shape[0] != n):
+        raise ValueError("objects must be a contiguous (n, in_stride) uint8 array")
+    results = np.zeros(n, dtype=INSERT_RESULT_DTYPE)
+    raw = InsertReportStruct()
+    rc = lib.stormck_insert_host(buf.ctypes.data, ctypes.byref(layout), int(space_id), ctypes.byref(params.raw),
+                                 keys.ctypes.data, stride, offsets.ctypes.data if offsets is not None else None,
+                                 lens.ctypes.data if lens is not None else None, length, n,
+                                 objects.ctypes.data if n else None, int(objects.shape[1]), flags,
+                                 results.ctypes.data if n else None, ctypes.byref(raw), threads)
+    return results, _insert_report(rc, raw)
